@@ -74,6 +74,10 @@ def main() -> None:
     ap.add_argument("--no-full-step", action="store_true", help="skip the full_step / roofline_mfma legs (BASELINE configs[2]: the whole "
                     "training iteration with the three StyleUNets, ~15 s) -- profiling runs of the rasterizer")
     ap.add_argument("--no-stress", action="store_true", help="skip the stress_1m_2048 leg (BASELINE configs[4] on one GPU, ~3 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what its LAST step computed -- the "
+                    "view's colour, depth and alpha images, the radii and the per-Gaussian gradients a caller receives -- as DIR/<name>.npy "
+                    "(float32; rank 0 at N > 1): the inputs are seeded, so two builds can be compared output for output -- the images and radii "
+                    "exactly, the gradients within a tolerance (they are summed with float atomics, in an order that varies from run to run)")
     ap.add_argument("--_cpu-worker", dest="cpu_worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_worker:                                    # child process of a cpu_baseline_* leg (no GPU work)
@@ -165,9 +169,11 @@ def main() -> None:
         h = handles.get((v, k))
         if h is None:
             h = handles[(v, k)] = fused.prepare(settings[v], g_color, g_depth, g_alpha, k)
-        _, _, _, _, g = fused.run(h, det[0], det[1], det[2], det[3], det[4], inputs_outlive_join=True)
+        res = fused.run(h, det[0], det[1], det[2], det[3], det[4], inputs_outlive_join=True)
         if world > 1:
+            g = res[4]
             exchange(k, [g["dL_dmeans3D"], g["dL_dscales"], g["dL_drotations"], g["dL_dopacity"], g["dL_dcolors"]], fused.slots[k]["stream"])
+        return res                     # (color, depth, alpha, radii, per-Gaussian gradients): what --dump-outputs writes
 
     def step_operator_on(i: int):
         r = rasterizers[(i * world + rank) % len(rasterizers)]
@@ -177,8 +183,11 @@ def main() -> None:
         torch.autograd.backward([color, depth, alpha], [g_color, g_depth, g_alpha])
         if world > 1:
             exchange(i % n_slots, [means3D.grad, scales.grad, rotations.grad, opacities.grad, colors.grad], torch.cuda.current_stream(dev))
+        res = (color, depth, alpha, radii, dict(zip(DUMP_GRADS, (means2D.grad, means3D.grad, scales.grad, rotations.grad, opacities.grad,
+                                                                 colors.grad))))
         for leaf in leaves:
             leaf.grad = None
+        return res
 
     def step_operator(i: int):
         if streams is None:
@@ -186,7 +195,7 @@ def main() -> None:
         st = streams[i % len(streams)]
         st.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(st):
-            step_operator_on(i)
+            return step_operator_on(i)
 
     step = step_operator if args.operator_path else step_fused
 
@@ -216,12 +225,24 @@ def main() -> None:
     if xchg is not None:
         xchg.reset()                    # N > 1: the timed region starts on an iteration boundary of the exchange
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
+    if args.dump_outputs and rank == 0 and last is not None and not args.operator_path:
+        # the last view's own gradients, copied before sync_all(): its join() adds the other slots' sums into slot 0's buffers.  The slot's
+        # view is collected first (should it not have fit its binning buffer it is redone then, on the slot's stream), then copied there
+        sl = fused.slots[(args.warmup + args.steps - 1) % len(fused.slots)]
+        fused._collect(sl)
+        with torch.cuda.stream(sl["stream"]):
+            last = last[:4] + ({n: last[4][n].clone() for n in DUMP_GRADS},)
     sync_all()
     elapsed = time.perf_counter() - t0
     prof = _lib.prof_collect()
     _lib.prof_enable([])
+    dumped = None
+    if args.dump_outputs and rank == 0 and last is not None:
+        # copied now: the next steps reuse the slot's images
+        dumped = dump_outputs(args.dump_outputs, last, (args.warmup + args.steps - 1) * world % len(settings))
     # stability evidence for short timed regions (the driver's --steps 20 is a 3-ms region that includes the fill and drain of the
     # stream pipeline): the same number of steps again, five more times, each block timed like the region above
     value_blocks = []
@@ -533,6 +554,8 @@ def main() -> None:
         out["exchange_styleunet"] = exchange_leg
     if exchange_check is not None:
         out["exchange_check"] = exchange_check
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if world == 1 and not args.no_full_step:
         # BASELINE configs[2] and the MFMA roofline north_star asks for, measured in this process (about 15 s): the whole training
         # iteration at the reference's batch shape (1 view per step) and at 4 views of one pose per step, and the convolution kernels'
@@ -561,6 +584,26 @@ def main() -> None:
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+# per-Gaussian gradients of a step as the caller receives them (FusedRasterStep.run's sums / the autograd leaves' .grad)
+DUMP_GRADS = ("dL_dmeans2D", "dL_dmeans3D", "dL_dscales", "dL_drotations", "dL_dopacity", "dL_dcolors")
+
+
+def dump_outputs(out_dir: str, last, view: int):
+    """--dump-outputs: the last timed step's results as float32 .npy files (40 MB at the headline size, under the 64-MB budget).  The
+    images and radii repeat bit for bit with the same arguments; the gradients are float-atomic sums whose order varies from run to run, so
+    they repeat to rounding (about 1e-7 of their largest magnitude), not bit for bit."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    color, depth, alpha, radii, g = last
+    files = {}
+    for name, t in (("color", color), ("depth", depth), ("alpha", alpha), ("radii", radii), *((n, g[n]) for n in DUMP_GRADS)):
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        files[name] = list(a.shape)
+    return {"dir": out_dir, "view": view, "dtype": "float32", "arrays": files,
+            "bytes": int(sum(4 * int(np.prod(s)) for s in files.values()))}
 
 
 VALU_PEAK_LANE_OPS = 78.6e12   # MI355X_MICROARCH.md: 157.3 TFLOP/s fp32 vector = 256 CUs x 4 SIMDs x 32 lanes x 2.4 GHz fused multiply-adds

@@ -39,6 +39,7 @@ python profiles/conv_launch_table.py $O/conv_launches_split_f16.csv 2>&1 | grep 
 AG_CONV_MATH=f16 python profiles/conv_launch_table.py $O/conv_launches_f16.csv 2>&1 | grep -v amdgpu.ids > $O/conv_launch_table_f16.txt
 head -4 $O/conv_launch_table_split_f16.txt; head -3 $O/conv_launch_table_f16.txt | tail -2
 python profiles/per_view_breakdown.py 1 3 2>&1 | grep -v "amdgpu.ids\|Warning\|_warn_once" > $O/per_view_breakdown.txt; head -3 $O/per_view_breakdown.txt
+[ -x profiles/ub/mfma_floor_f16 ] || ${HIPCC:-/opt/rocm/bin/hipcc} --offload-arch=gfx950 -O3 -o profiles/ub/mfma_floor_f16 profiles/ub/mfma_floor_f16.hip   # build product, not in git
 ./profiles/ub/mfma_floor_f16 > $O/mfma_floor_f16.txt 2>&1; tail -3 $O/mfma_floor_f16.txt
 python profiles/step_glue_sources.py 1 2>&1 | grep -v "amdgpu.ids\|Warning\|_warn_once" > $O/glue_sources.txt; head -3 $O/glue_sources.txt
 ( time python -m pytest tests -m gpu -q 2>&1 | tail -4 ) > $O/gputests_head.txt 2>&1; cat $O/gputests_head.txt

@@ -196,3 +196,93 @@ def assert_rows_close(got, ref, name, rtol=1e-4, row_rtol=1e-5):
     assert worst <= 1.0, f"{name}: {int((d > lim).sum())} of {d.size} over tolerance, worst ratio {worst:.2f}, max |diff| {d.max():.3e}"
 
 
+
+
+# ---- the reference build's results on two scenes, stored as fixtures (tests/golden/make_golden_ref_live.py) ----------------------------
+def live_scene(name):
+    """The seeded scenes of tests/golden/ref_live_<name>.npz: ``config1`` (BASELINE.json configs[0]: 10k random Gaussians, one 512x512
+    camera) and ``long_lists`` (tile lists longer than one 256-entry batch, near-plane culling, off-screen splats, a ragged image)."""
+    from animatablegaussians_amd import synth
+    if name == "config1":
+        sc = synth.random_gaussians()
+    elif name == "long_lists":
+        sc = synth.random_gaussians(P=6000, img=200, focal=180.0)
+        sc["img_w"], sc["img_h"] = 200, 120
+        sc["intr"] = np.array([[180.0, 0, 100], [0, 180.0, 60], [0, 0, 1]], np.float32)
+        sc["means3D"][:, :2] *= 0.35
+        sc["means3D"][::7, 2] += 2.45           # a band of Gaussians at / behind the near plane
+        sc.update(synth.upstream_grads(200, 120, 99))
+    else:
+        raise KeyError(name)
+    return sc, cam_of(sc)
+
+
+def bits_digest(a):
+    """SHA-256 of an array's values for bit-for-bit comparison against a stored fixture: float32 by its bits, integers and booleans by value
+    (as int64), the shape included."""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        assert a.dtype == np.float32, a.dtype
+        body = a.view(np.uint32).tobytes()
+    else:
+        body = a.astype(np.int64).tobytes()
+    return hashlib.sha256(repr(a.shape).encode() + body).hexdigest()
+
+
+# ---- render3 through the drop-in: the native call it issues (tests/test_dropin_cpu.py, tests/golden/make_golden_dropin.py) ---------------
+def render3_cases():
+    """Seeded inputs of ``render3(vals, bg, extr, intr, 512, 480, 1.0)``: a colour call and a spherical-harmonics call."""
+    import torch
+    g = torch.Generator().manual_seed(5)
+    P = 37
+    base = {"positions": torch.randn(P, 3, generator=g) + torch.tensor([0., 0., 3.]), "opacity": torch.rand(P, 1, generator=g),
+            "scales": torch.rand(P, 3, generator=g) * 0.05, "rotations": torch.nn.functional.normalize(torch.randn(P, 4, generator=g)),
+            "max_sh_degree": 0}
+    extr = torch.eye(4)
+    extr[:3, :3] = torch.tensor([[0.8, 0., 0.6], [0., 1., 0.], [-0.6, 0., 0.8]])
+    extr[:3, 3] = torch.tensor([0.1, -0.2, 2.5])
+    intr = torch.tensor([[1100., 0., 250.], [0., 1090., 260.], [0., 0., 1.]])
+    bg = torch.tensor([0.1, 0.2, 0.3])
+    cases = []
+    for variant in ("colors", "shs"):
+        vals = dict(base)
+        if variant == "colors":
+            vals["colors"] = torch.rand(P, 3, generator=g)
+        else:
+            vals["shs"] = torch.randn(P, 3, 4, generator=g) * 0.3
+            vals["max_sh_degree"] = 1
+        cases.append((variant, (vals, bg, extr, intr, 512, 480, 1.0)))
+    return cases
+
+
+class NativeCallRecorder:
+    """Replaces ``rasterizer.native_rasterize_gaussians`` (the ``_C.rasterize_gaussians`` equivalent) by a recorder of its arguments and maps
+    ``.cuda()`` / ``zeros_like(device=...)`` to the CPU, for as long as the ``with`` block runs."""
+
+    def __enter__(self):
+        import torch
+        from animatablegaussians_amd import rasterizer as rz
+        self.calls = []
+
+        def recorder(*args, **kw):
+            self.calls.append((args, kw))
+            H, W, P = int(args[12]), int(args[13]), args[1].shape[0]
+            z = lambda *s: torch.zeros(*s)  # noqa: E731
+            return (0, 0), z(3, H, W), z(1, H, W), z(1, H, W), torch.zeros(P, dtype=torch.int32), z(1), z(1), z(1)
+
+        def zeros_like_cpu(t, **kw):
+            kw.pop("device", None)
+            return self._real[2](t, **kw)
+
+        self._real = (rz.native_rasterize_gaussians, torch.Tensor.cuda, torch.zeros_like)
+        rz.native_rasterize_gaussians = recorder
+        torch.Tensor.cuda = lambda self_, *a, **k: self_
+        torch.zeros_like = zeros_like_cpu
+        return self
+
+    def __exit__(self, *exc):
+        import torch
+        from animatablegaussians_amd import rasterizer as rz
+        rz.native_rasterize_gaussians, torch.Tensor.cuda, torch.zeros_like = self._real
+        return False

@@ -86,6 +86,64 @@ def test_bench_json_line():
     assert 1.0 < lp["views_per_s_1view_per_step"] <= f["views_per_s_1view_per_step"] * 1.1
 
 
+
+def test_bench_dump_outputs_are_the_last_steps_own(tmp_path):
+    """--dump-outputs writes what the LAST timed step computed: one view's images, radii and per-Gaussian gradients, float32, within 64 MB.
+    20 + 62 - 1 = 81 puts that step on stream slot 0 of three, the slot whose gradient buffers FusedRasterStep.join() sums the other
+    slots into at the end of the timed region; the dump must hold the view's own gradients all the same.  Checked against a fresh
+    one-view FusedRasterStep.view() of the same view and inputs: images and radii to 1e-6, gradients to 1e-4 of their largest magnitude
+    (float-atomic sums in another order; the sum over three views would be off by its own magnitude)."""
+    import numpy as np
+    import torch
+
+    from animatablegaussians_amd import camera, synth
+    from animatablegaussians_amd.rasterizer import FusedRasterStep, GaussianRasterizationSettings
+    dump, warmup, steps = tmp_path / "outputs", 20, 62
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--no-full-step", "--no-stress", "--no-cpu-baseline", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["roofline"]["launches_timed"] == steps and d["config"]["streams"] == 3
+    assert (warmup + steps - 1) % d["config"]["streams"] == 0                     # the last step ran on slot 0
+    du = d["dumped_outputs"]
+    view = (warmup + steps - 1) % d["config"]["views"]
+    P, side = d["config"]["gaussians"], 1024
+    want = {"color": [3, side, side], "depth": [1, side, side], "alpha": [1, side, side], "radii": [P], "dL_dmeans2D": [P, 3],
+            "dL_dmeans3D": [P, 3], "dL_dscales": [P, 3], "dL_drotations": [P, 4], "dL_dopacity": [P, 1], "dL_dcolors": [P, 3]}
+    assert du["view"] == view and du["arrays"] == want and du["bytes"] <= 64 << 20
+    assert sorted(os.listdir(dump)) == sorted(f"{k}.npy" for k in want)
+    a = {k: np.load(dump / f"{k}.npy") for k in want}
+    for k, v in a.items():
+        assert v.dtype == np.float32 and list(v.shape) == want[k] and np.isfinite(v).all(), k
+
+    # the same view through a fresh one-slot step, with bench.py's seeded inputs
+    dev = torch.device("cuda", 0)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    av = synth.avatar_map_gaussians()
+    c = synth.free_view_cameras(8, img=side)[view]
+    cm = camera.camera_from_intr_extr(c["extr"], c["intr"], side, side)
+    rs = GaussianRasterizationSettings(image_height=side, image_width=side, tanfovx=cm["tanfovx"], tanfovy=cm["tanfovy"], bg=t(av["bg"]),
+                                       scale_modifier=1.0, viewmatrix=t(cm["viewmatrix"]), projmatrix=t(cm["projmatrix"]), sh_degree=0,
+                                       campos=t(cm["campos"]), prefiltered=False, debug=False)
+    up = synth.upstream_grads(side, side, 12345)
+    one = FusedRasterStep(P, side, side, dev, n_streams=1)
+    color, depth, alpha, radii, g = one.view(rs, t(av["means3D"]), t(av["colors"]), t(av["opacities"]), t(av["scales"]), t(av["rotations"]),
+                                             t(up["dL_dcolor"]), t(up["dL_ddepth"]), t(up["dL_dalpha"]))
+    torch.cuda.synchronize(dev)
+    ref = {"color": color, "depth": depth, "alpha": alpha, "radii": radii, **{k: g[k] for k in want if k.startswith("dL_")}}
+    ref = {k: v.float().cpu().numpy().reshape(want[k]) for k, v in ref.items()}
+    assert (ref["radii"] > 0).any() and np.abs(ref["color"]).max() > 0
+    for k in ("color", "depth", "alpha", "radii"):
+        np.testing.assert_allclose(a[k], ref[k], rtol=0, atol=1e-6, err_msg=k)
+    for k in want:
+        if k.startswith("dL_"):
+            m = float(np.abs(ref[k]).max())
+            assert m > 0 and float(np.abs(a[k].astype(np.float64) - ref[k]).max()) <= 1e-4 * m, k
+
+
 def test_bench_two_ranks_control_flow_on_one_gpu():
     """The N > 1 launch exactly as the driver issues it (python -m torch.distributed.run, one rank per process), with the gloo
     transport so that both ranks can share this box's single GPU: a functional check of the sharded path, the max-over-ranks timing
