@@ -1,0 +1,712 @@
+"""The 8-channel head and the view-feature path of the avatar's StyleUNets against the float64 CPU oracle, layer by layer and end to end.
+
+network/avatar.py:34-36 builds three DualStyleUNets: position_net (out_ch 3), other_net (out_ch 8: ToRGB heads of 32 rows, 8 x 4 Haar sub-bands)
+and color_net (out_ch 3, plus a view-direction feature added after decoder stage 4, dual_styleunet.py:881-883).  test_styleunet_net.py pins
+out_ch = 3 without view features to the reference module's golden; the grouped and one-network paths are otherwise compared with each other
+only.  Here the yardstick is oracle/dual_styleunet_oracle.py (itself pinned to the reference module's golden by test_styleunet_oracle_cpu.py),
+run live on the CPU in float64 for the values and in float32 for the tolerance ("as close as fp32 allows", the golden's err32):
+
+  A. layer level, at the product's shapes: the 32-row ToRGB (fused_layers.to_rgb) of every decoder stage; the grouped ToRGB over the run
+     layout the grouped chain builds for [position, color, other]; the view-feature entry (grouped._SelectAddRows); the comb convolution that
+     follows it on both paths the code has (_SelectAddRows + _GroupedComb, and _CatLevels + one convolution).  Bar per tensor:
+     max|ours - o64| / max|o64| <= 4 x (the same for the fp32 oracle) + 2e-6.
+  B. end to end: AvatarNet.get_maps, grouped chain and one network at a time, in the three arithmetic modes, forward maps and every parameter,
+     pose-map and view-feature gradient; plus two views of the colour network in one grouped call (the render_views path).  Bars are those of
+     test_styleunet_net.py::_golden_body with the live fp32 oracle as err32.
+
+The networks get three different synth.named_fill seeds (equal weights would hide a member mix-up between position_net and color_net) and
+keep the fill's non-zero biases and noise strengths."""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+MODES = ["split_f16", "fp32", "split_bf16"]
+SEEDS = {"position_net": 1101, "color_net": 2202, "other_net": 3303}
+NETS = ("position_net", "other_net", "color_net")            # the order get_maps returns the maps in
+
+
+def _torch():
+    import torch
+    return torch
+
+
+class _Math:
+    def __init__(self, mode):
+        self.mode = mode
+
+    def __enter__(self):
+        from animatablegaussians_amd import conv as agc
+        self.prev = agc.set_math(self.mode)
+
+    def __exit__(self, *exc):
+        from animatablegaussians_amd import conv as agc
+        agc.set_math(self.prev)
+
+
+def _rel(got, ref):
+    """max|got - ref| / max|ref| in float64 (``ref`` a CPU float64 tensor)."""
+    got = got.detach().double().cpu()
+    return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-300)
+
+
+def _check_layer(tag, got, o64, o32):
+    """Per tensor: ours within 4x the fp32 oracle's deviation from the float64 oracle, + 2e-6.  Prints the measured values."""
+    worst = 0.0
+    for k in o64:
+        assert got.get(k) is not None, (tag, k)
+        d, d32 = _rel(got[k], o64[k]), _rel(o32[k], o64[k])
+        lim = 4 * d32 + 2e-6
+        worst = max(worst, d / lim)
+        print(f"[layer] {tag} {k}: ours {d:.2e} oracle-fp32 {d32:.2e} ours/bar {d / lim:.2f}")
+        assert d <= lim, (tag, k, d, d32)
+    return worst
+
+
+def _cpu_threads():
+    """CPUs this process may use: the affinity mask, capped by a cgroup CPU quota (a container can see hundreds of CPUs and be allowed 16; torch's
+    default of one thread per visible CPU then spends the oracle's time throttled)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    return n
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _oracle_threads():
+    torch = _torch()
+    prev = torch.get_num_threads()
+    torch.set_num_threads(_cpu_threads())
+    yield
+    torch.set_num_threads(prev)
+
+
+def _oracle_sd(sd, dt):
+    return {k: v.detach().to(dt).clone().requires_grad_(True) for k, v in sd.items()}
+
+
+@pytest.fixture(scope="module")
+def nets_cpu():
+    """One out_ch = 3 and one out_ch = 8 network (shapes only) and the three fills, {name: reference state dict}."""
+    torch = _torch()
+    from animatablegaussians_amd import synth
+    from animatablegaussians_amd.styleunet import DualStyleUNet
+    n3 = DualStyleUNet(inp_size=512, inp_ch=3, out_ch=3, out_size=1024, style_dim=512, n_mlp=2)
+    n8 = DualStyleUNet(inp_size=512, inp_ch=3, out_ch=8, out_size=1024, style_dim=512, n_mlp=2)
+    sd3, sd8 = n3.reference_state_dict(), n8.reference_state_dict()
+    fills = {"position_net": synth.named_fill(sd3, seed=SEEDS["position_net"]), "color_net": synth.named_fill(sd3, seed=SEEDS["color_net"]),
+             "other_net": synth.named_fill(sd8, seed=SEEDS["other_net"])}
+    return {"n3": n3, "n8": n8, "fills": fills}
+
+
+def _stages(net):
+    """(stage, Cin of the ToRGB, H) of every decoder stage, from the built network."""
+    return [(n, cout, int(net._p(f"noises.noise_{2 * n + 1}").shape[-1])) for n, _, cout in net.dec]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# A.1  the 32-row ToRGB (other_net's heads) at every decoder stage
+# ---------------------------------------------------------------------------------------------------------------------------------
+_TORGB_KEYS = ("conv.weight", "conv.modulation.weight", "conv.modulation.bias", "bias")
+
+
+def _oracle_to_rgb(params, x, skip, w_latent, g, dt):
+    """DualStyleUNetOracle.to_rgb for stacked members: params[m] = {key: tensor} (keys under the prefix "h"), x [M, ...], skip [M, ...] or None,
+    w_latent[m].  -> {name: float64 tensor}: output, input / skip gradients, every parameter gradient of every member."""
+    torch = _torch()
+    from oracle.dual_styleunet_oracle import DualStyleUNetOracle
+    xs = x.detach().to(dt).requires_grad_(True)
+    ss = skip.detach().to(dt).requires_grad_(True) if skip is not None else None
+    sds = [_oracle_sd({f"h.{k}": v for k, v in p.items()}, dt) for p in params]
+    outs = [DualStyleUNetOracle(sd).to_rgb(xs[m:m + 1], "h", w_latent[m].to(dt), ss[m:m + 1] if ss is not None else None) for m, sd in enumerate(sds)]
+    out = torch.cat(outs, 0)
+    (out * g.to(dt)).sum().backward()
+    res = {"out": out.detach().double(), "grad x": xs.grad.double()}
+    if ss is not None:
+        res["grad skip"] = ss.grad.double()
+    for m, sd in enumerate(sds):
+        for k in _TORGB_KEYS:
+            res[f"grad m{m} {k}"] = sd[f"h.{k}"].grad.double()
+    return res
+
+
+@pytest.fixture(scope="module")
+def torgb32_cases(nets_cpu):
+    """Per decoder stage of a 512 -> 1024 network: other_net's to_rgbs1 head at that stage, inputs, and the oracle in float64 / float32.
+    Stage 0 has no skip (dual_styleunet.py:888), every later one has."""
+    torch = _torch()
+    net, fill = nets_cpu["n8"], nets_cpu["fills"]["other_net"]
+    cases = []
+    for n, cin, H in _stages(net):
+        g = torch.Generator().manual_seed(500 + n)
+        p = {k: fill[f"to_rgbs1.{n}.{k}"] for k in _TORGB_KEYS}
+        cout = int(p["conv.weight"].shape[1])
+        x = torch.randn(1, cin, H, H, generator=g)
+        skip = torch.randn(1, cout, H // 2, H // 2, generator=g) if n > 0 else None
+        wl = [torch.randn(1, 512, generator=g)]
+        up = torch.randn(1, cout, H, H, generator=g)
+        cases.append(dict(n=n, cin=cin, H=H, cout=cout, params=[p], x=x, skip=skip, wl=wl, up=up,
+                          o64=_oracle_to_rgb([p], x, skip, wl, up, torch.float64), o32=_oracle_to_rgb([p], x, skip, wl, up, torch.float32)))
+    return cases
+
+
+def _product_params(params, dev):
+    return [{k: v.detach().to(dev).clone().requires_grad_(True) for k, v in p.items()} for p in params]
+
+
+def _product_style(p, wl):
+    from animatablegaussians_amd import linear_ops
+    return linear_ops.equal_linear_group(wl, [p["conv.modulation.weight"]], [p["conv.modulation.bias"]])[0]
+
+
+def _grads_of(ps, out, x, skip):
+    res = {"out": out.detach(), "grad x": x.grad}
+    if skip is not None:
+        res["grad skip"] = skip.grad
+    for m, p in enumerate(ps):
+        for k in _TORGB_KEYS:
+            res[f"grad m{m} {k}"] = p[k].grad
+    return res
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_to_rgb_32_rows_every_stage_vs_oracle(mode, torgb32_cases):
+    """fused_layers.to_rgb with Cout = 32 (other_net's heads, 8 x 4 Haar sub-bands): modulated 1 x 1 convolution + bias + the wavelet skip,
+    at every decoder stage's (Cin, H) of the 512 -> 1024 network; the style through the product's EqualLinear so the modulation weight and
+    bias gradients are checked too."""
+    torch = _torch()
+    from animatablegaussians_amd import fused_layers
+    from oracle.dual_styleunet_oracle import _fir
+    dev = torch.device("cuda:0")
+    k_up = _fir(gain=4.0).to(dev)
+    assert [c["cout"] for c in torgb32_cases] == [32] * len(torgb32_cases)
+    with _Math(mode):
+        for c in torgb32_cases:
+            (p,) = _product_params(c["params"], dev)
+            x = c["x"].to(dev).requires_grad_(True)
+            skip = c["skip"].to(dev).requires_grad_(True) if c["skip"] is not None else None
+            style = _product_style(p, c["wl"][0].to(dev))
+            w = p["conv.weight"]
+            out = fused_layers.to_rgb(x, w, style, p["bias"].reshape(-1), skip, k_up, 1 / math.sqrt(w.shape[2] * w.shape[-1] * w.shape[-1]))
+            out.backward(c["up"].to(dev))
+            torch.cuda.synchronize()
+            _check_layer(f"to_rgb32 {mode} stage {c['n']} Cin {c['cin']} H {c['H']}", _grads_of([p], out, x, skip), c["o64"], c["o32"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# A.2  the grouped ToRGB over the run layout of [position, color, other]: widths 12 12 12 12 32 32 in one call
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _members():
+    """(network name, branch) of the grouped chain's decoder members, in its order: networks as GroupedStyleUNets gets them from
+    AvatarNet._grouped_nets, two branches each."""
+    return [(name, b) for name in ("position_net", "color_net", "other_net") for b in (1, 2)]
+
+
+@pytest.fixture(scope="module")
+def grouped_torgb_cases(nets_cpu):
+    torch = _torch()
+    from animatablegaussians_amd import grouped
+    fills = nets_cpu["fills"]
+    members = _members()
+    out_ch = {"position_net": nets_cpu["n3"].out_ch, "color_net": nets_cpu["n3"].out_ch, "other_net": nets_cpu["n8"].out_ch}
+    runs = grouped._runs([out_ch[name] for name, _ in members])
+    cases = []
+    for n, cin, H in _stages(nets_cpu["n8"]):
+        if n not in (0, 2, 4, 5):                 # no skip; 64^2; the view stage; the last stage at 512^2
+            continue
+        g = torch.Generator().manual_seed(700 + n)
+        params = [{k: fills[name][f"to_rgbs{b}.{n}.{k}"] for k in _TORGB_KEYS} for name, b in members]
+        x = torch.randn(len(members), cin, H, H, generator=g)
+        wl = [torch.randn(1, 512, generator=g) for _ in members]
+        couts = [int(p["conv.weight"].shape[1]) for p in params]
+        skips = [torch.randn(e - s, couts[s], H // 2, H // 2, generator=g) if n > 0 else None for s, e in runs]
+        ups = [torch.randn(e - s, couts[s], H, H, generator=g) for s, e in runs]
+        # the oracle per run (the runs have different widths), then merged into one dict
+        o = {}
+        for dt in (torch.float64, torch.float32):
+            res = {}
+            for r, (s, e) in enumerate(runs):
+                part = _oracle_to_rgb(params[s:e], x[s:e], skips[r], wl[s:e], ups[r], dt)
+                res[f"out run {r}"] = part.pop("out")
+                res[f"grad x run {r}"] = part.pop("grad x")
+                if n > 0:
+                    res[f"grad skip run {r}"] = part.pop("grad skip")
+                for k, v in part.items():
+                    m = int(k.split()[1][1:])
+                    res[k.replace(f"m{m} ", f"m{s + m} ")] = v
+            o[dt] = res
+        cases.append(dict(n=n, cin=cin, H=H, runs=runs, couts=couts, params=params, x=x, wl=wl, skips=skips, ups=ups,
+                          o64=o[torch.float64], o32=o[torch.float32]))
+    return cases
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_grouped_to_rgb_runs_of_mixed_widths_vs_oracle(mode, grouped_torgb_cases):
+    """grouped.grouped_to_rgb_runs with the run layout GroupedStyleUNets builds for [position, color, other] (grouped._runs over the members'
+    out_ch: 12 12 12 12 | 32 32 rows) in ONE call; every member against its own oracle head -- outputs, the input gradient (written by the runs
+    into one tensor), the skip gradients per run and each member's weight / modulation / bias gradients."""
+    torch = _torch()
+    from animatablegaussians_amd import grouped
+    from oracle.dual_styleunet_oracle import _fir
+    dev = torch.device("cuda:0")
+    k_up = _fir(gain=4.0).to(dev)
+    for c in grouped_torgb_cases:
+        assert c["runs"] == [(0, 4), (4, 6)] and c["couts"] == [12, 12, 12, 12, 32, 32], (c["runs"], c["couts"])
+    with _Math(mode):
+        for c in grouped_torgb_cases:
+            ps = _product_params(c["params"], dev)
+            x = c["x"].to(dev).requires_grad_(True)
+            skips = [s.to(dev).requires_grad_(True) if s is not None else None for s in c["skips"]]
+            styles = [_product_style(p, wl.to(dev)) for p, wl in zip(ps, c["wl"])]
+            w0 = ps[0]["conv.weight"]
+            outs = grouped.grouped_to_rgb_runs(x, c["runs"], [p["conv.weight"] for p in ps], styles, [p["bias"].reshape(-1) for p in ps], skips,
+                                               k_up, 1 / math.sqrt(w0.shape[2]))
+            torch.autograd.backward(list(outs), [u.to(dev) for u in c["ups"]])
+            torch.cuda.synchronize()
+            got = {}
+            for r, o in enumerate(outs):
+                s, e = c["runs"][r]
+                got[f"out run {r}"] = o.detach()
+                got[f"grad x run {r}"] = x.grad[s:e]
+                if skips[r] is not None:
+                    got[f"grad skip run {r}"] = skips[r].grad
+            for m, p in enumerate(ps):
+                for k in _TORGB_KEYS:
+                    got[f"grad m{m} {k}"] = p[k].grad
+            _check_layer(f"grouped to_rgb {mode} stage {c['n']} Cin {c['cin']} H {c['H']}", got, c["o64"], c["o32"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# A.4  the view-feature entry: x[m] = out[src[m]] (+ bilinear(vf[m - r0]) on rows [r0, r1))
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _select_add_reference(out, vf, src, rows):
+    """Plain torch: row gather, F.interpolate(..., mode="bilinear") (dual_styleunet.py:881-883), add on the row range."""
+    torch = _torch()
+    import torch.nn.functional as F
+    x = out[list(src)]
+    if vf is None:
+        return x
+    v = vf if tuple(vf.shape[-2:]) == tuple(out.shape[-2:]) else F.interpolate(vf, tuple(out.shape[-2:]), mode="bilinear")
+    r0, r1 = rows
+    return torch.cat([x[:r0], x[r0:r1] + v, x[r1:]], 0)
+
+
+# (rows of the shared state, C, H, W), src, row range, view feature (h, w)
+_SELECT_CASES = [
+    ((6, 128, 256, 256), (0, 1, 2, 3, 4, 5), (2, 4), (128, 128)),                # the product: one view, 128^2 -> 256^2
+    ((6, 128, 256, 256), (0, 1, 2, 3, 2, 3, 4, 5), (2, 6), (128, 128)),          # two views of the colour network
+    ((6, 128, 256, 256), (0, 1, 2, 3, 4, 5), (2, 4), (256, 256)),                # the feature at the target resolution
+    ((3, 8, 37, 50), (1, 0, 2, 2), (1, 3), (19, 24)),                            # odd sizes, a non-integer ratio, unsorted sources
+]
+
+
+@pytest.mark.parametrize("case", range(len(_SELECT_CASES)))
+def test_select_add_rows_vs_float64_torch(case):
+    """grouped._SelectAddRows (linear_ops.select_add_rows: ag_select_add_rows, the resize inside the row copy) forward and backward against
+    float64 torch.  Rows outside the range must be exact copies of their source (no view feature); the gradient with respect to ``vf`` is the
+    adjoint of the resize."""
+    torch = _torch()
+    from animatablegaussians_amd import grouped
+    shape, src, rows, vhw = _SELECT_CASES[case]
+    g = torch.Generator().manual_seed(900 + case)
+    out = torch.randn(*shape, generator=g)
+    vf = torch.randn(rows[1] - rows[0], shape[1], *vhw, generator=g)
+    up = torch.randn(len(src), *shape[1:], generator=g)
+    ref = {}
+    for dt in (torch.float64, torch.float32):
+        o, v = out.detach().to(dt).requires_grad_(True), vf.detach().to(dt).requires_grad_(True)
+        x = _select_add_reference(o, v, src, rows)
+        (x * up.to(dt)).sum().backward()
+        ref[dt] = {"x": x.detach().double(), "grad out": o.grad.double(), "grad vf": v.grad.double()}
+    dev = torch.device("cuda:0")
+    o, v = out.to(dev).requires_grad_(True), vf.to(dev).requires_grad_(True)
+    x = grouped._SelectAddRows.apply(o, v, tuple(src), rows)
+    x.backward(up.to(dev))
+    torch.cuda.synchronize()
+    _check_layer(f"select_add_rows case {case}", {"x": x.detach(), "grad out": o.grad, "grad vf": v.grad}, ref[torch.float64], ref[torch.float32])
+    for m, s in enumerate(src):
+        if not rows[0] <= m < rows[1]:
+            assert torch.equal(x[m].detach(), o[s].detach()), m
+    # the adjoint identity <resize(v), u> = <v, resize^T(u)> in float64, on the members' rows
+    r0, r1 = rows
+    lhs = float((ref[torch.float64]["x"][r0:r1] - out.double()[list(src[r0:r1])]).mul(up.double()[r0:r1]).sum())
+    prod = vf.double() * v.grad.double().cpu()
+    rhs = float(prod.sum())
+    assert abs(lhs - rhs) <= 1e-6 * float(prod.abs().sum()), (lhs, rhs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# A.5  the comb convolution after the view feature, on both paths
+# ---------------------------------------------------------------------------------------------------------------------------------
+# members' networks (0 position, 1 color, 2 other), the shared-state row each continues, the view-feature rows; spatial size (None: the product's)
+_COMB_CASES = {
+    "one_view": ((0, 0, 1, 1, 2, 2), (0, 1, 2, 3, 4, 5), (2, 4), None),
+    "two_views": ((0, 0, 1, 1, 1, 1, 2, 2), (0, 1, 2, 3, 2, 3, 4, 5), (2, 6), 64),
+    "unsorted": ((1, 1, 0, 0, 2, 2), (2, 3, 0, 1, 4, 5), (0, 2), 64),
+}
+
+
+@pytest.fixture(scope="module")
+def comb_cases(nets_cpu):
+    """The view-dependent stage's comb convolution (comb_convs.0 of a 512 -> 1024 network: cat(stage-4 state 128 ch, level 128 ch) -> 128 at
+    256^2) with each network's filled weights, inputs per layout, and the oracle's conv_layer on cat([out + interp(vf), level]) in float64 /
+    float32 with every gradient."""
+    torch = _torch()
+    import torch.nn.functional as F
+    from oracle.dual_styleunet_oracle import DualStyleUNetOracle
+    net = nets_cpu["n3"]
+    n = net.VIEW_STAGE + 1
+    prefix = f"comb_convs.{net.n_comb - 1 - n}"
+    fills = nets_cpu["fills"]
+    wts = [{"c.0.weight": fills[name][f"{prefix}.0.weight"], "c.1.bias": fills[name][f"{prefix}.1.bias"]} for name in ("position_net", "color_net", "other_net")]
+    cout, cin = int(wts[0]["c.0.weight"].shape[0]), int(wts[0]["c.0.weight"].shape[1])
+    c1 = int(net.dec[net.VIEW_STAGE][2])                                     # the stage-4 state's channels
+    H0 = int(net._p(f"noises.noise_{2 * net.VIEW_STAGE + 1}").shape[-1])      # its resolution
+    vf_ch = 128                                                              # get_viewdir_feat: [1, 128, S/8, S/8]
+    assert c1 == vf_ch and cin == 2 * c1, (c1, cin)
+    cases = {}
+    for i, (key, (net_idx, src, rows, H)) in enumerate(_COMB_CASES.items()):
+        H = H or H0
+        g = torch.Generator().manual_seed(1300 + i)
+        out = torch.randn(6, c1, H, H, generator=g)
+        lev = torch.randn(3, cin - c1, H, H, generator=g)
+        vf = torch.randn(rows[1] - rows[0], c1, H // 2, H // 2, generator=g) * 0.5
+        up = torch.randn(len(src), cout, H, H, generator=g)
+        o = {}
+        for dt in (torch.float64, torch.float32):
+            sds = [_oracle_sd(w, dt) for w in wts]
+            ot, lt, vt = (t.detach().to(dt).requires_grad_(True) for t in (out, lev, vf))
+            ys = []
+            for m, (r, s) in enumerate(zip(net_idx, src)):
+                a = ot[s:s + 1]
+                if rows[0] <= m < rows[1]:
+                    a = a + F.interpolate(vt[m - rows[0]:m - rows[0] + 1], a.shape[-2:], mode="bilinear")
+                ys.append(DualStyleUNetOracle(sds[r]).conv_layer(torch.cat([a, lt[r:r + 1]], 1), "c"))
+            y = torch.cat(ys, 0)
+            if dt == torch.float64:
+                # no upstream gradient where the float64 pre-activation is within 1e-4 of the largest from zero: there two correct fp32
+                # evaluations pick different leaky-ReLU slopes (the oracle's own fp32 run is 3e-2 of max|grad| off on this layer without the
+                # mask, measured) and no yardstick is left; 1e-4 is ~300x the fp32 forward deviation (3e-7)
+                up = up * (y.detach().abs() > 1e-4 * float(y.detach().abs().max())).float()
+            (y * up.to(dt)).sum().backward()
+            res = {"out": y.detach().double(), "grad state": ot.grad.double(), "grad level": lt.grad.double(), "grad vf": vt.grad.double()}
+            for r, sd in enumerate(sds):
+                res[f"grad net{r} weight"] = sd["c.0.weight"].grad.double()
+                res[f"grad net{r} bias"] = sd["c.1.bias"].grad.double()
+            o[dt] = res
+        cases[key] = dict(net_idx=net_idx, src=src, rows=rows, H=H, out=out, lev=lev, vf=vf, up=up, wts=wts, o64=o[torch.float64], o32=o[torch.float32])
+    return cases
+
+
+def _comb_product(path, out, lev, vf, src, net_idx, rows, ws, bs):
+    """A COPY of the comb part of grouped.GroupedStyleUNets._stage (member ranges, the resize before _CatLevels, the scale) on one of its two
+    paths: this test checks the kernels and autograd nodes it calls; _stage's own wiring of them is covered by the end-to-end tests below."""
+    from animatablegaussians_amd import grouped
+    M = len(src)
+    scale = 1 / math.sqrt(ws[0].shape[1] * 9)
+    if path == "split":                           # _SelectAddRows, then ag_grouped_comb_* (the level half once per network)
+        assert list(net_idx) == sorted(net_idx)
+        x = grouped._SelectAddRows.apply(out, vf, tuple(src), rows)
+        used = sorted(set(net_idx))
+        begin = [list(net_idx).index(r) for r in used] + [M]
+        return grouped._GroupedComb.apply(tuple(begin), scale, x, lev, *[ws[r] for r in used], *[bs[r] for r in net_idx])
+    v = grouped.bilinear_resize(vf, out.shape[-2:])                          # the concatenating fallback
+    cat = grouped._CatLevels.apply(out, lev, v, tuple(src), tuple(net_idx), rows)
+    return grouped.grouped_conv_layer(cat, [ws[r] for r in net_idx], [bs[r] for r in net_idx], None, scale, False)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("layout,path", [("one_view", "split"), ("one_view", "cat"), ("two_views", "split"), ("two_views", "cat"), ("unsorted", "cat")])
+def test_comb_convolution_after_the_view_feature_vs_oracle(layout, path, mode, comb_cases):
+    """The view-dependent stage's input: the view feature added to the colour members' rows, then the comb convolution with the encoder level
+    -- _SelectAddRows + _GroupedComb (the default) and _CatLevels + one convolution (set_comb_split(False), or members whose network indices are
+    not sorted) -- against the oracle's conv_layer on cat([out + interp(vf), level]).  Layouts: one view; two views of the colour network (a
+    network feeding four rows, shared-state rows read twice); networks out of order (the fallback with the feature on rows 0..1)."""
+    torch = _torch()
+    from animatablegaussians_amd import grouped
+    c = comb_cases[layout]
+    dev = torch.device("cuda:0")
+    ws = [w["c.0.weight"].to(dev).requires_grad_(True) for w in c["wts"]]
+    bs = [w["c.1.bias"].to(dev).requires_grad_(True) for w in c["wts"]]
+    out, lev, vf = (c[k].to(dev).requires_grad_(True) for k in ("out", "lev", "vf"))
+    prev = grouped.set_comb_split(path == "split")
+    try:
+        with _Math(mode):
+            y = _comb_product(path, out, lev, vf, c["src"], c["net_idx"], c["rows"], ws, bs)
+            y.backward(c["up"].to(dev))
+            torch.cuda.synchronize()
+    finally:
+        grouped.set_comb_split(prev)
+    got = {"out": y.detach(), "grad state": out.grad, "grad level": lev.grad, "grad vf": vf.grad}
+    for r in range(len(ws)):
+        got[f"grad net{r} weight"] = ws[r].grad
+        got[f"grad net{r} bias"] = bs[r].grad
+    _check_layer(f"comb {layout} {path} {mode}", got, c["o64"], c["o32"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# B.  the product chain of all three networks, end to end
+# ---------------------------------------------------------------------------------------------------------------------------------
+FULL_MULT = 5.0                        # full-tensor statistics: ours within 5x the fp32 oracle's at p50 / p90 / p99
+FULL_CAP = {"sum": 1e-2, "blk": 2e-2, "sq": 2e-2}
+FULL_CAP_SCALAR = 8e-2                 # one-element tensors (noise strengths): relative error of the number (sq: 2x)
+NBLK = 16
+# One named exception to the caps, for these seeds.  position_net's convs1.11.activate.bias (64 numbers, so a "block" is 4 channels): block 11
+# deviates by 1.72e-2 of its magnitude in the fp32 oracle, the fp32 oracle with the comb convolutions re-associated AND the product in split_f16
+# -- identical to four digits in three different arithmetics -- 0.93e-2 in the product's fp32 mode, 2.44e-2 in split_bf16 (one network).  The
+# channel sums are ill-conditioned (sum|terms| / |sum| up to 1.4e4 in float64); the product's own reduction matches a float64 sum of its own
+# pre-activation gradient to 1e-9 of sum|terms|; the deviation is leaky-ReLU slope selections at pre-activations within fp32 rounding of zero,
+# each moving the block by a fixed amount: a handful of pixels, not arithmetic error.  Cap for this one statistic: 2x the fp32 oracle's 1.72e-2.
+FULL_CAP_NAMED = {("position_net", "convs1.11.activate.bias", "blk"): 3.5e-2}
+
+
+def _sub(t, n=256):
+    f = t.detach().flatten()
+    step = max(1, f.numel() // n)
+    return f[::step][:n].double().cpu()
+
+
+def _summary(g):
+    """What the comparison reads of one gradient tensor: 256 samples, max |g|, and full-tensor statistics in float64 -- the sum, the sums of
+    16 contiguous blocks (dimension 0, output channels, slowest), their sums of magnitudes, the sum of squares."""
+    torch = _torch()
+    g = g.detach().double().flatten()
+    n = g.numel()
+    edges = [(n * b) // NBLK for b in range(NBLK + 1)]
+    blk = torch.stack([g[edges[b]:edges[b + 1]].sum() for b in range(NBLK)]).cpu()
+    blkabs = torch.stack([g[edges[b]:edges[b + 1]].abs().sum() for b in range(NBLK)]).cpu()
+    return {"sub": _sub(g), "max": float(g.abs().max()), "sum": float(g.sum()), "abs": float(g.abs().sum()), "blk": blk, "blkabs": blkabs,
+            "sq": float((g * g).sum()), "n": n}
+
+
+def _deviation(s, ref):
+    """(sample deviation / max|ref|, block-sum, sum and square-sum deviations) of summary ``s`` from the float64 oracle's ``ref``."""
+    d = float((s["sub"] - ref["sub"]).abs().max()) / max(ref["max"], 1e-30)
+    d_sum = abs(s["sum"] - ref["sum"]) / max(ref["abs"], 1e-300)
+    d_blk = float(((s["blk"] - ref["blk"]).abs() / ref["blkabs"].clamp_min(1e-300)).max())
+    d_sq = abs(s["sq"] - ref["sq"]) / max(ref["sq"], 1e-300)
+    return d, d_sum, d_blk, d_sq
+
+
+def _oracle_net(sd_gpu, style, pose, up, vfs, dt, learn):
+    """One network through the oracle on the CPU in ``dt`` -> (images float64, {key: gradient}, pose gradient, (vf1 grad, vf2 grad) or None)."""
+    torch = _torch()
+    from oracle.dual_styleunet_oracle import DualStyleUNetOracle
+    sd = {k: v.detach().cpu().to(dt).clone().requires_grad_(k in learn) for k, v in sd_gpu.items()}
+    p = pose.detach().cpu().to(dt).requires_grad_(True)
+    vs = [v.detach().cpu().to(dt).requires_grad_(True) for v in vfs] if vfs else None
+    img = DualStyleUNetOracle(sd).forward(style.detach().cpu().to(dt), p, *(vs or (None, None)))
+    (img * up.to(dt)).sum().backward()
+    grads = {k: sd[k].grad for k in learn}
+    return img.detach().double(), grads, p.grad.double(), ([v.grad.double() for v in vs] if vs else None)
+
+
+@pytest.fixture(scope="module")
+def avatar():
+    """AvatarNet.synthetic with view directions, the three networks filled with three seeds, eval mode (colour style = the fixed buffer); the
+    pose map and two cameras' view features (detached), fixed upstream gradients."""
+    torch = _torch()
+    from animatablegaussians_amd import synth
+    from animatablegaussians_amd.avatar import AvatarNet
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_avatar_net_gpu import _items
+    torch.manual_seed(31359)
+    net = AvatarNet.synthetic({'with_viewdirs': True})
+    for name, seed in SEEDS.items():
+        sub = getattr(net, name)
+        sub.load_reference_state_dict(synth.named_fill(sub.reference_state_dict(), seed=seed))
+    net.eval()
+    items = _items(net)
+    net.get_pose_map(items)
+    pose = items['smpl_pos_map'][:3].contiguous()
+    with torch.no_grad():
+        fv, bv = (t.detach().contiguous() for t in net.get_viewdir_feat(items))
+        cam = synth.free_view_cameras(3, img=1024)[1]
+        items2 = {**items, 'extr': torch.from_numpy(np.ascontiguousarray(cam["extr"])).float().cuda(),
+                  'intr': torch.from_numpy(np.ascontiguousarray(cam["intr"])).float().cuda()}
+        fv2, bv2 = (t.detach().contiguous() for t in net.get_viewdir_feat(items2))
+    assert float((fv2 - fv).abs().max()) > 1e-3 * float(fv.abs().max())        # a second view that differs
+    g = torch.Generator().manual_seed(11)
+    ups = {name: torch.randn(1, 2 * getattr(net, name).out_ch * 1, 1024, 1024, generator=g) for name in NETS}
+    up_color2 = torch.randn(1, 6, 1024, 1024, generator=g)
+    return dict(net=net, pose=pose, fv=fv, bv=bv, fv2=fv2, bv2=bv2, ups=ups, up_color2=up_color2)
+
+
+@pytest.fixture(scope="module")
+def oracle_runs(avatar):
+    """The three networks through the oracle, float64 and float32 (the yardstick), on the same state dicts; the colour network also for the
+    second view (float64: its map and view-feature gradients).  Keeps per-tensor summaries, not the gradients."""
+    torch = _torch()
+    net = avatar["net"]
+    res = {"maps": {}, "err32_map": {}, "grads": {}, "pose": None, "pose32": None, "vf": None}
+    pose64 = pose32 = 0
+    for name in NETS:
+        sub = getattr(net, name)
+        sd = sub.reference_state_dict()
+        learn = list(sub._learnable)
+        style = getattr(net, name.replace("_net", "_style"))
+        vfs = (avatar["fv"], avatar["bv"]) if name == "color_net" else None
+        img64, g64, p64, v64 = _oracle_net(sd, style, avatar["pose"][None], avatar["ups"][name], vfs, torch.float64, learn)
+        s64 = {k: _summary(g64[k]) for k in learn}
+        del g64
+        img32, g32, p32, v32 = _oracle_net(sd, style, avatar["pose"][None], avatar["ups"][name], vfs, torch.float32, learn)
+        e32 = {k: _deviation(_summary(g32[k]), s64[k]) for k in learn}
+        del g32
+        res["maps"][name] = img64
+        res["err32_map"][name] = _rel(img32, img64)
+        res["grads"][name] = (learn, s64, e32)
+        pose64, pose32 = pose64 + p64, pose32 + p32
+        if v64 is not None:
+            res["vf"] = v64
+            res["vf32"] = v32
+    res["pose"], res["pose32"] = pose64, pose32
+    img, _, _, v = _oracle_net(net.color_net.reference_state_dict(), net.color_style, avatar["pose"][None], avatar["up_color2"],
+                               (avatar["fv2"], avatar["bv2"]), torch.float64, list(net.color_net._learnable))
+    res["color_view2"], res["vf_view2"] = img, v
+    return res
+
+
+def _check_maps(maps, oracle, tag):
+    for name, m in zip(NETS, maps):
+        ref = oracle["maps"][name]
+        assert tuple(m.shape) == tuple(ref.shape), (name, tuple(m.shape))
+        d = _rel(m, ref)
+        print(f"[e2e] {tag} forward {name}: ours {d:.2e} oracle-fp32 {oracle['err32_map'][name]:.2e} (bar 1e-4)")
+        assert d <= 1e-4, (tag, name, d)
+
+
+def _check_vf_grad(got, ref, what):
+    """An ACTIVATION gradient (2 M elements): leaky-ReLU slope flips near zero make isolated elements differ by factors, so relative L2 and the
+    fraction of elements off by more than 1e-3 of the largest (the bars of test_grouped_gpu.py::test_three_networks_as_one_chain...)."""
+    got = got.detach().double().cpu()
+    l2 = float((got - ref).norm() / ref.norm())
+    off = float(((got - ref).abs() > 1e-3 * float(ref.abs().max())).double().mean())
+    print(f"[e2e] {what}: relative L2 {l2:.2e} (bar 3e-3), fraction off by > 1e-3 of max {off:.2e} (bar 5e-3)")
+    assert l2 <= 3e-3 and off <= 5e-3, (what, l2, off)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("grouped", [True, False], ids=["grouped", "one_network"])
+def test_three_networks_end_to_end_vs_oracle(grouped, mode, avatar, oracle_runs):
+    """AvatarNet.get_maps -- the grouped chain (comb split on, as by default) or one network at a time -- forward maps of all three networks,
+    every channel, and after a backward of fixed upstream gradients every parameter gradient of every network, the pose-map gradient (summed over
+    the three networks) and both view-feature gradients, against the float64 oracle; the float32 oracle is the yardstick."""
+    torch = _torch()
+    net = avatar["net"]
+    prev = net.set_grouped(grouped)
+    try:
+        with _Math(mode):
+            net.zero_grad(set_to_none=True)
+            # (the grouped chain's encoder reads the pose map as ONE input shared by the three networks and gives it no gradient -- the product
+            # computes it under no_grad: grouped._GroupedLayer refuses; the one-network path carries it)
+            pose = avatar["pose"].clone().requires_grad_(not grouped)
+            fv, bv = avatar["fv"].clone().requires_grad_(True), avatar["bv"].clone().requires_grad_(True)
+            maps = net.get_maps(pose, fv, bv)
+            torch.autograd.backward(list(maps), [avatar["ups"][name].cuda() for name in NETS])
+            torch.cuda.synchronize()
+    finally:
+        net.set_grouped(prev)
+    tag = f"{mode} {'grouped' if grouped else 'one network'}"
+    _check_maps(maps, oracle_runs, tag)
+    del maps
+
+    for name in NETS:
+        sub = getattr(net, name)
+        learn, s64, e32 = oracle_runs["grads"][name]
+        rows, full = [], []
+        for k in learn:
+            gk = sub._p(k).grad
+            assert gk is not None, (name, k)
+            d, d_sum, d_blk, d_sq = _deviation(_summary(gk), s64[k])
+            r, r_sum, r_blk, r_sq = e32[k]
+            rows.append((d, r, k))
+            full.append((k, d_sum, r_sum, d_blk, r_blk, d_sq, r_sq, s64[k]["n"]))
+        ours, ref = np.array([o for o, _, _ in rows]), np.array([r for _, r, _ in rows])
+        print(f"[e2e] {tag} {name}: gradient rows over {len(rows)} tensors, ours / oracle fp32: "
+              + " ".join(f"p{q} {np.percentile(ours, q):.2e}/{np.percentile(ref, q):.2e}" for q in (50, 75, 90, 95, 99, 100)))
+        for q in (50, 75, 90, 95):
+            assert np.percentile(ours, q) <= 3 * np.percentile(ref, q), (name, q, np.percentile(ours, q), np.percentile(ref, q))
+        tens = [(o, r) for o, r, k in rows if not k.endswith("noise.weight")]
+        o99, r99 = np.percentile([o for o, _ in tens], 99), np.percentile([r for _, r in tens], 99)
+        assert o99 <= 3 * r99, (name, o99, r99)
+        # per-tensor caps of _golden_body: 1e-2, and 5e-2 for the noise strengths -- except a noise strength on which the fp32 oracle ITSELF
+        # misses 5e-2 (a one-number gradient, a sum over a whole map with cancellation): 2x the oracle's own deviation there.  Measured: other_net
+        # convs2.11.noise.weight, oracle fp32 0.142 of the value, ours 0.128-0.149 in the three modes on both paths; no other tensor
+        for o, r, k in rows:
+            cap = 1e-2
+            if k.endswith("noise.weight"):
+                cap = 2 * r if r > 5e-2 else 5e-2
+            assert o <= cap, (name, k, o, r)
+        fo = {kk: np.array([r[i] for r in full]) for kk, i in (("sum", 1), ("rsum", 2), ("blk", 3), ("rblk", 4), ("sq", 5), ("rsq", 6))}
+        print(f"[e2e] {tag} {name}: full-tensor statistics, ours/oracle fp32 at p50 p90 p99 max: "
+              + "; ".join(f"{kk}: " + " ".join(f"{np.percentile(fo[kk], q):.1e}/{np.percentile(fo['r' + kk], q):.1e}" for q in (50, 90, 99, 100))
+                          for kk in ("sum", "blk", "sq"))
+              + " | p99 ratio " + " ".join(f"{kk} {np.percentile(fo[kk], 99) / max(np.percentile(fo['r' + kk], 99), 1e-7):.2f}" for kk in ("sum", "blk", "sq")))
+        for kk in ("sum", "blk", "sq"):
+            for q in (50, 90, 99):
+                assert np.percentile(fo[kk], q) <= FULL_MULT * max(np.percentile(fo["r" + kk], q), 1e-7), (name, kk, q, np.percentile(fo[kk], q),
+                                                                                                         np.percentile(fo["r" + kk], q))
+            col = {"sum": 1, "blk": 3, "sq": 5}[kk]
+            for r in full:
+                cap = (2 * FULL_CAP_SCALAR if kk == "sq" else FULL_CAP_SCALAR) if r[7] == 1 else FULL_CAP[kk]
+                cap = FULL_CAP_NAMED.get((name, r[0], kk), cap)
+                if r[7] == 1 and r[0].endswith("noise.weight") and r[col + 1] > cap:
+                    cap = 2 * r[col + 1]          # the noise-strength rule of the rows above: the fp32 oracle itself misses the cap (convs2.11, 0.142)
+                assert r[col] <= cap, (name, kk, r)
+
+    for got, ref, what in ((fv.grad, oracle_runs["vf"][0], "front view-feature gradient"), (bv.grad, oracle_runs["vf"][1], "back view-feature gradient")):
+        _check_vf_grad(got, ref, f"{tag} {what}")
+    net.zero_grad(set_to_none=True)
+    if grouped:
+        assert pose.grad is None
+        return
+    # the pose-map gradient, summed over the three networks: by distribution over 12 288 samples (deviation / max|grad|), cap on the maximum
+    ref = oracle_runs["pose"][0, :, ::8, ::8]
+    scale = float(oracle_runs["pose"].abs().max())
+    pose_dev = ((pose.grad[:, ::8, ::8].double().cpu() - ref).abs() / scale).flatten().numpy()
+    ref32 = ((oracle_runs["pose32"][0, :, ::8, ::8] - ref).abs() / scale).flatten().numpy()
+    print(f"[e2e] {tag} pose-map gradient deviation / max: " + " ".join(f"p{q} {np.percentile(pose_dev, q):.2e}/{np.percentile(ref32, q):.2e}"
+                                                                         for q in (50, 90, 99, 99.9, 100)))
+    assert np.percentile(pose_dev, 99) <= 1.5e-3 and np.percentile(pose_dev, 99.9) <= 6e-3, (np.percentile(pose_dev, 99), np.percentile(pose_dev, 99.9))
+    assert pose_dev.max() <= 3e-2, pose_dev.max()
+    # full-tensor statistics of the pose-map gradient (the "@pose" row of _golden_body), per-tensor caps
+    s64 = _summary(oracle_runs["pose"])
+    d, d_sum, d_blk, d_sq = _deviation(_summary(pose.grad), s64)
+    _, r_sum, r_blk, r_sq = _deviation(_summary(oracle_runs["pose32"]), s64)
+    print(f"[e2e] {tag} pose-map gradient full statistics, ours/oracle fp32: sum {d_sum:.1e}/{r_sum:.1e} blk {d_blk:.1e}/{r_blk:.1e} sq {d_sq:.1e}/{r_sq:.1e}")
+    assert d_sum <= FULL_CAP["sum"] and d_blk <= FULL_CAP["blk"] and d_sq <= FULL_CAP["sq"], (d_sum, d_blk, d_sq)
+
+
+def test_two_views_in_one_grouped_call_vs_oracle_per_view(avatar, oracle_runs):
+    """GroupedStyleUNets.forward with {color: [(f1, b1), (f2, b2)]} (the render_views path: shared stages once, the view-dependent stage once
+    per view): each view's colour map and view-feature gradients against the oracle run for that view; the position and other maps are still
+    the oracle's."""
+    torch = _torch()
+    net = avatar["net"]
+    gn = net._grouped_nets()
+    assert gn is not None
+    net.zero_grad(set_to_none=True)
+    x = avatar["pose"][None].contiguous()
+    feats = [tuple(avatar[k].clone().requires_grad_(True) for k in pair) for pair in (("fv", "bv"), ("fv2", "bv2"))]
+    pm, cms, om = gn.forward([net.position_style, net.color_style, net.other_style], x, {1: feats})
+    assert isinstance(cms, list) and len(cms) == 2
+    torch.autograd.backward([pm, cms[0], cms[1], om], [avatar["ups"]["position_net"].cuda(), avatar["ups"]["color_net"].cuda(),
+                                                       avatar["up_color2"].cuda(), avatar["ups"]["other_net"].cuda()])
+    torch.cuda.synchronize()
+    _check_maps((pm, om, cms[0]), oracle_runs, "two views (view 1)")
+    d = _rel(cms[1], oracle_runs["color_view2"])
+    print(f"[e2e] two views: colour map of view 2 {d:.2e} (bar 1e-4)")
+    assert d <= 1e-4, d
+    for v, (f, b) in enumerate(feats):
+        ref = oracle_runs["vf"] if v == 0 else oracle_runs["vf_view2"]
+        _check_vf_grad(f.grad, ref[0], f"two views: view {v + 1} front view-feature gradient")
+        _check_vf_grad(b.grad, ref[1], f"two views: view {v + 1} back view-feature gradient")
+    net.zero_grad(set_to_none=True)

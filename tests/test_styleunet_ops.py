@@ -340,7 +340,7 @@ def test_skip_chain_taps_reproduce_the_reference_chain_on_the_cpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("C,h,w", [(3, 8, 8), (3, 33, 17), (1, 1, 1), (3, 256, 256)])
+@pytest.mark.parametrize("C,h,w", [(3, 8, 8), (3, 33, 17), (1, 1, 1), (3, 256, 256), (8, 16, 16), (8, 256, 256), (8, 33, 17)])
 def test_skip_chain_kernel_equals_the_three_kernel_path_and_the_oracle(C, h, w):
     """ag_skip_chain_forward / _backward against (a) the three kernels they replace (block merge, upfirdn2d up = 2, block split) with
     their autograd, (b) the float64 oracle chain; accumulate mode adds into an existing output."""
