@@ -1,5 +1,6 @@
 """Shared helpers of the parity tests (tests only)."""
 import ctypes
+import os
 
 import numpy as np
 
@@ -286,3 +287,16 @@ class NativeCallRecorder:
         from animatablegaussians_amd import rasterizer as rz
         rz.native_rasterize_gaussians, torch.Tensor.cuda, torch.zeros_like = self._real
         return False
+
+
+def cpu_threads():
+    """CPUs this process may use: the affinity mask, capped by a cgroup CPU quota (a container can see hundreds of CPUs and be allowed 16; torch's
+    default of one thread per visible CPU then spends a CPU oracle's time throttled)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    return n

@@ -22,6 +22,7 @@ import sys
 
 import numpy as np
 import pytest
+from helpers import cpu_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -67,24 +68,11 @@ def _check_layer(tag, got, o64, o32):
     return worst
 
 
-def _cpu_threads():
-    """CPUs this process may use: the affinity mask, capped by a cgroup CPU quota (a container can see hundreds of CPUs and be allowed 16; torch's
-    default of one thread per visible CPU then spends the oracle's time throttled)."""
-    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    try:
-        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
-        if quota != "max":
-            n = min(n, max(1, int(int(quota) // int(period))))
-    except (OSError, ValueError):
-        pass
-    return n
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _oracle_threads():
     torch = _torch()
     prev = torch.get_num_threads()
-    torch.set_num_threads(_cpu_threads())
+    torch.set_num_threads(cpu_threads())
     yield
     torch.set_num_threads(prev)
 
