@@ -218,12 +218,16 @@ SYMBOLS = [
     ("ag_smplx_prepare", ctypes.c_int, [ctypes.POINTER(AgSmplxModel), c_vp, c_vp, c_vp]),
     ("ag_smplx_shape", ctypes.c_int, [ctypes.POINTER(AgSmplxModel), c_i32, c_vp, c_vp, c_vp]),
     ("ag_mat4_mul_inverse", ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    ("ag_mat4_mul_inverse_backward", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    ("ag_smplx_backward", ctypes.c_int, [ctypes.POINTER(AgSmplxModel), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("ag_smplx_keypoints", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     # include/ag_avatar.h
     ("ag_gather_activate_forward", ctypes.c_int, [ctypes.POINTER(AgGatherArgs), c_vp]),
     ("ag_gather_activate_backward", ctypes.c_int, [ctypes.POINTER(AgGatherArgs), c_vp, c_vp, c_vp, c_vp]),
     ("ag_lbs_forward", ctypes.c_int, [ctypes.POINTER(AgLbsArgs), c_vp]),
     ("ag_lbs_backward", ctypes.c_int, [ctypes.POINTER(AgLbsArgs), c_vp, c_vp, c_vp]),
+    ("ag_lbs_backward_joints_workspace_bytes", c_sz, [c_i32, c_i32]),
+    ("ag_lbs_backward_joints", ctypes.c_int, [ctypes.POINTER(AgLbsArgs), c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     ("ag_hand_fuse", ctypes.c_int, [ctypes.POINTER(AgHandFuseArgs), c_vp]),
     # include/ag_styleunet.h
     ("ag_fused_bias_act", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_f, ctypes.c_int64, ctypes.c_int64, c_i32, c_vp]),

@@ -297,11 +297,11 @@ class AvatarNet(nn.Module):
     def lbs(self):
         return self.core.lbs
 
-    @torch.no_grad()
     def _blend_points(self, jnt_mats, vectors=None):
-        """(no grad) LBS of the canonical points, optionally of direction vectors with the rotation part only
-        (:127-129,151-152) -- on the skinning kernel: the reference's einsum over [N, 55] x [55, 16] lands on a skinny
-        library GEMM that takes 3.5 ms per call at N = 268 k (profiles/r01f), the fused kernel ~20 us."""
+        """LBS of the canonical points, optionally of direction vectors with the rotation part only (:127-129,151-152) -- on the
+        skinning kernel: the reference's einsum over [N, 55] x [55, 16] lands on a skinny library GEMM that takes 3.5 ms per call at
+        N = 268 k (profiles/r01f), the fused kernel ~20 us.  Differentiable with respect to ``jnt_mats`` (as the reference's einsum);
+        the canonical points are buffers and get no gradient."""
         N = self.core.xyz.shape[0]
         if not hasattr(self, "_unit_quat") or self._unit_quat.shape[0] != N:
             q = torch.zeros(N, 4, device=self.core.xyz.device)
@@ -324,9 +324,10 @@ class AvatarNet(nn.Module):
             idx = self._mask_index64 = self.core.pix.long()
         return idx
 
-    @torch.no_grad()
     def get_pose_map(self, items):
-        """Live position map [6, S/2, S/2] from ``cano2live_jnt_mats_woRoot``  (:149-159)."""
+        """Live position map [6, S/2, S/2] from ``cano2live_jnt_mats_woRoot``  (:149-159).  Differentiable with respect to those
+        matrices, as in the reference (test-time pose refinement); with gradients disabled, or matrices that do not require grad, it
+        runs the same launches as a no-grad call."""
         live_pts, _ = self._blend_points(items['cano2live_jnt_mats_woRoot'])
         H, W = self.map_shape
         live = torch.zeros(H, W, 3, device=live_pts.device)
@@ -453,7 +454,9 @@ class AvatarNet(nn.Module):
                 [x, front_viewdirs, back_viewdirs])
             return position_map, other_map, color_map
         color_style = torch.rand_like(self.color_style) if self.random_style and self.training else self.color_style
-        grouped = self._grouped_nets()
+        # a pose map that requires grad (pose refinement: get_pose_map of matrices that require grad) feeds the three networks as one
+        # SHARED input, which the grouped executor cannot differentiate: the networks then run one by one (their input gradients add up)
+        grouped = self._grouped_nets() if not (x.requires_grad and torch.is_grad_enabled()) else None
         if grouped is not None:                      # the three networks as ONE launch chain (grouped.py): G = 3 encoders, G = 6 decoders
             vf = {1: (front_viewdirs, back_viewdirs)} if front_viewdirs is not None else None
             # (frozen: in eval mode the three styles are this module's buffers -- the weights' modulation / maxima / packed images persist between frames)
@@ -595,7 +598,7 @@ class AvatarNet(nn.Module):
             for f, b in feats:
                 (cm,) = self._graphed(("color_view", f is not None), view_fn, [f, b])
                 color_maps.append(cm.clone())     # the capture's output buffer is reused by the next view
-        elif self._grouped_nets() is not None:
+        elif self._grouped_nets() is not None and not (x.requires_grad and torch.is_grad_enabled()):     # (see get_maps)
             color_style = torch.rand_like(self.color_style) if self.random_style and self.training else self.color_style
             vf = {1: [fb for fb in feats]} if self.with_viewdirs else {1: [(None, None)] * len(feats)}
             position_map, color_maps, other_map = self._grouped_nets().forward([self.position_style, color_style, self.other_style], x, vf,

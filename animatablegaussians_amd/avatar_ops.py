@@ -2,7 +2,8 @@
 
 ``gather_activate`` is the fused equivalent of ``AvatarNet.get_positions`` + ``get_others`` + ``get_colors`` applied to
 already-computed StyleUNet outputs (reference ``network/avatar.py:93-124``); ``lbs_transform`` is
-``AvatarNet.transform_cano2live`` (``network/avatar.py:84-91``).  Python only allocates and passes pointers.
+``AvatarNet.transform_cano2live`` (``network/avatar.py:84-91``), differentiable with respect to the joint matrices as well
+(pose refinement).  Python only allocates and passes pointers.
 """
 from __future__ import annotations
 
@@ -242,15 +243,32 @@ class _LbsTransform(torch.autograd.Function):
         N, J, dev = int(positions.shape[0]), int(lbs.shape[1]), positions.device
         g_p = _chk(g_p, "grad") if g_p is not None else torch.zeros_like(positions)
         g_r = _chk(g_r, "grad") if g_r is not None else torch.zeros_like(rotations)
-        dp, dr = torch.empty_like(positions), torch.empty_like(rotations)
         a = _lbs_args(N, J, lbs, jnt_mats, positions, rotations, g_p, g_r, ctx.sparse)
+        if not ctx.needs_input_grad[3]:
+            dp, dr = torch.empty_like(positions), torch.empty_like(rotations)
+            with _lib.on_device(dev):
+                _lib.check(L.ag_lbs_backward(ctypes.byref(a), _p(dp), _p(dr), _stream(dev)), "ag_lbs_backward")
+            return dp, dr, None, None, None
+        # the joint matrices require grad (pose refinement): the same pass also reduces dL/d jnt_mats (include/ag_avatar.h)
+        want_pr = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]          # both or neither (include/ag_avatar.h)
+        dp = torch.empty_like(positions) if want_pr else None
+        dr = torch.empty_like(rotations) if want_pr else None
+        dj = torch.empty_like(jnt_mats)
+        ws_bytes = int(L.ag_lbs_backward_joints_workspace_bytes(N, J))
+        ws = torch.empty((max(ws_bytes // 4, 1),), dtype=torch.float32, device=dev)
+        null = ctypes.c_void_p(None)
         with _lib.on_device(dev):
-            _lib.check(L.ag_lbs_backward(ctypes.byref(a), _p(dp), _p(dr), _stream(dev)), "ag_lbs_backward")
-        return dp, dr, None, None, None   # lbs weights and joint matrices are data, not parameters
+            _lib.check(L.ag_lbs_backward_joints(ctypes.byref(a), _p(dp) if dp is not None else null, _p(dr) if dr is not None else null,
+                                                _p(dj), _p(ws), ws_bytes, _stream(dev)), "ag_lbs_backward_joints")
+        return (dp if ctx.needs_input_grad[0] else None), (dr if ctx.needs_input_grad[1] else None), None, dj, None
 
 
 def lbs_transform(positions, rotations, lbs, jnt_mats, sparse=None):
-    """-> (live positions [N,3], live rotations [N,4]).  ``sparse``: ``SparseLbs.build(lbs)`` (or None: dense rows)."""
+    """-> (live positions [N,3], live rotations [N,4]).  ``sparse``: ``SparseLbs.build(lbs)`` (or None: dense rows).
+
+    Differentiable with respect to ``positions``, ``rotations`` and ``jnt_mats`` (row 3 of dL/d jnt_mats is 0: the forward does not
+    read it).  When ``jnt_mats`` does not require grad the backward is the plain ``ag_lbs_backward`` launch.  The blend weights
+    ``lbs`` get no gradient (None), as they are not optimised (the reference trainer only collects ``avatar_net.parameters()``)."""
     return _LbsTransform.apply(positions, rotations, lbs, jnt_mats, sparse)
 
 

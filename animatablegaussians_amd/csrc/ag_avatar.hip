@@ -310,6 +310,197 @@ __global__ void __launch_bounds__(256) lbs_backward_kernel(AgLbsArgs a, float* _
     g_rotations[4 * n + 3] = two_s * dk - t2 * k;
 }
 
+// The chain of lbs_backward_kernel for one Gaussian with its blended matrix M, extended by GM[12] = dL/dM (3x4) with JOINTS -- the
+// per-Gaussian term of the joint-matrix gradient dL/dA_j = sum_n w_nj GM_n.  lbs_backward_joints_kernel calls it with null position /
+// rotation outputs: those come from lbs_backward_kernel itself (ag_lbs_backward_joints), so that they are ag_lbs_backward's bits.
+template <bool JOINTS>
+__device__ __forceinline__ void lbs_backward_gaussian(const AgLbsArgs& a, int n, const float (&M)[12], float* __restrict__ g_positions,
+                                                      float* __restrict__ g_rotations, float (&GM)[12])
+{
+    // positions: dL/dp = M3^T g
+    const float gx = a.out_positions[3 * n], gy = a.out_positions[3 * n + 1], gz = a.out_positions[3 * n + 2];
+    if (g_positions) {
+        g_positions[3 * n + 0] = M[0] * gx + M[4] * gy + M[8] * gz;
+        g_positions[3 * n + 1] = M[1] * gx + M[5] * gy + M[9] * gz;
+        g_positions[3 * n + 2] = M[2] * gx + M[6] * gy + M[10] * gz;
+    }
+    if constexpr (JOINTS) {
+        // live p = M3 p + M[:, 3]  ->  dL/dM = g (x) [p, 1]
+        const float p[3] = { a.positions[3 * n], a.positions[3 * n + 1], a.positions[3 * n + 2] };
+        const float g[3] = { gx, gy, gz };
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) GM[4 * r + c] = g[r] * p[c];
+            GM[4 * r + 3] = g[r];
+        }
+    }
+
+    // rotations: recompute the forward, then walk the chain backwards
+    float q[4] = { a.rotations[4 * n], a.rotations[4 * n + 1], a.rotations[4 * n + 2], a.rotations[4 * n + 3] };
+    float R[9], two_s;
+    quat_to_mat(q, R, two_s);
+    float m[9];
+#pragma unroll
+    for (int x = 0; x < 3; x++)
+#pragma unroll
+        for (int z = 0; z < 3; z++) m[3 * x + z] = M[4 * x] * R[z] + M[4 * x + 1] * R[3 + z] + M[4 * x + 2] * R[6 + z];
+    const float x4[4] = { 1.0f + m[0] + m[4] + m[8], 1.0f + m[0] - m[4] - m[8], 1.0f - m[0] + m[4] - m[8], 1.0f - m[0] - m[4] + m[8] };
+    float qa[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) qa[c] = x4[c] > 0.f ? sqrtf(x4[c]) : 0.f;
+    int best = 0;
+#pragma unroll
+    for (int c = 1; c < 4; c++) if (qa[c] > qa[best]) best = c;
+    float cand[4];
+    if (best == 0)      { cand[0] = qa[0] * qa[0]; cand[1] = m[7] - m[5]; cand[2] = m[2] - m[6]; cand[3] = m[3] - m[1]; }
+    else if (best == 1) { cand[0] = m[7] - m[5]; cand[1] = qa[1] * qa[1]; cand[2] = m[3] + m[1]; cand[3] = m[2] + m[6]; }
+    else if (best == 2) { cand[0] = m[2] - m[6]; cand[1] = m[3] + m[1]; cand[2] = qa[2] * qa[2]; cand[3] = m[5] + m[7]; }
+    else                { cand[0] = m[3] - m[1]; cand[1] = m[6] + m[2]; cand[2] = m[7] + m[5]; cand[3] = qa[3] * qa[3]; }
+    const float qsel = qa[best];
+    const bool floored = !(qsel > 0.1f);
+    const float den = 2.0f * (floored ? 0.1f : qsel);
+    float go[4] = { a.out_rotations[4 * n], a.out_rotations[4 * n + 1], a.out_rotations[4 * n + 2], a.out_rotations[4 * n + 3] };
+    // out = cand / den
+    float gc[4], gden = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; c++) { gc[c] = go[c] / den; gden -= go[c] * cand[c] / (den * den); }
+    // den = 2 max(q_sel, 0.1): no gradient when the floor is active; the diagonal candidate is q_sel^2
+    float gq_sel = floored ? 0.f : 2.0f * gden;
+    gq_sel += 2.0f * qsel * gc[best];
+    // q_sel = sqrt(max(0, x_sel)) (zero sub-gradient at x <= 0)
+    const float gx_sel = (x4[best] > 0.f) ? gq_sel / (2.0f * qsel) : 0.f;
+    float gm[9];
+#pragma unroll
+    for (int c = 0; c < 9; c++) gm[c] = 0.f;
+    const float s0 = (best == 0 || best == 1) ? 1.f : -1.f;   // sign of m00 in x_best
+    const float s1 = (best == 0 || best == 2) ? 1.f : -1.f;   // sign of m11
+    const float s2 = (best == 0 || best == 3) ? 1.f : -1.f;   // sign of m22
+    gm[0] += s0 * gx_sel; gm[4] += s1 * gx_sel; gm[8] += s2 * gx_sel;
+    if (best == 0)      { gm[7] += gc[1]; gm[5] -= gc[1]; gm[2] += gc[2]; gm[6] -= gc[2]; gm[3] += gc[3]; gm[1] -= gc[3]; }
+    else if (best == 1) { gm[7] += gc[0]; gm[5] -= gc[0]; gm[3] += gc[2]; gm[1] += gc[2]; gm[2] += gc[3]; gm[6] += gc[3]; }
+    else if (best == 2) { gm[2] += gc[0]; gm[6] -= gc[0]; gm[3] += gc[1]; gm[1] += gc[1]; gm[5] += gc[3]; gm[7] += gc[3]; }
+    else                { gm[3] += gc[0]; gm[1] -= gc[0]; gm[6] += gc[1]; gm[2] += gc[1]; gm[7] += gc[2]; gm[5] += gc[2]; }
+    if constexpr (JOINTS) {
+        // m = M3 R  ->  dL/dM3 = gm R^T
+#pragma unroll
+        for (int x = 0; x < 3; x++)
+#pragma unroll
+            for (int y = 0; y < 3; y++) GM[4 * x + y] += gm[3 * x] * R[3 * y] + gm[3 * x + 1] * R[3 * y + 1] + gm[3 * x + 2] * R[3 * y + 2];
+    }
+    if (!g_rotations) return;
+    // m = M3 R  ->  dL/dR = M3^T gm
+    float G[9];
+#pragma unroll
+    for (int y = 0; y < 3; y++)
+#pragma unroll
+        for (int z = 0; z < 3; z++) G[3 * y + z] = M[y] * gm[z] + M[4 + y] * gm[3 + z] + M[8 + y] * gm[6 + z];
+    // R = I + two_s * U(q); dL/dq = two_s * dU^T G - two_s^2 q (U . G)
+    const float r = q[0], i = q[1], j = q[2], k = q[3];
+    const float U[9] = { -(j * j + k * k), i * j - k * r, i * k + j * r,
+                         i * j + k * r, -(i * i + k * k), j * k - i * r,
+                         i * k - j * r, j * k + i * r, -(i * i + j * j) };
+    float gs = 0.f;
+#pragma unroll
+    for (int c = 0; c < 9; c++) gs += G[c] * U[c];
+    const float dr = -k * G[1] + j * G[2] + k * G[3] - i * G[5] - j * G[6] + i * G[7];
+    const float di = j * G[1] + k * G[2] + j * G[3] - 2 * i * G[4] - r * G[5] + k * G[6] + r * G[7] - 2 * i * G[8];
+    const float dj = -2 * j * G[0] + i * G[1] + r * G[2] + i * G[3] + k * G[5] - r * G[6] + k * G[7] - 2 * j * G[8];
+    const float dk = -2 * k * G[0] - r * G[1] + i * G[2] + r * G[3] - 2 * k * G[4] + j * G[5] + i * G[6] + j * G[7];
+    const float t2 = two_s * two_s * gs;
+    g_rotations[4 * n + 0] = two_s * dr - t2 * r;
+    g_rotations[4 * n + 1] = two_s * di - t2 * i;
+    g_rotations[4 * n + 2] = two_s * dj - t2 * j;
+    g_rotations[4 * n + 3] = two_s * dk - t2 * k;
+}
+
+// Joint-matrix gradient, pass 1 (the blend and the rotation chain of lbs_backward_kernel again, plus the reduction of its workgroup): every workgroup writes its
+// slab [J][12] = sum over its 256 Gaussians of w_nj GM_n.  LDS: [4 waves][64][J] weight rows | [4][64][12] GM rows | [4][J][12] wave partials.
+// The sparse form is expanded into the dense row layout (zeros, then its K weights), so both forms run the same summation over the same
+// values in the same order: a skipped term is + 0 * GM, and the slabs are bit-identical.  Lane j of a wave sums its 64 rows in order;
+// the four wave partials are added in wave order.  No float atomics: the slabs are combined by lbs_joint_slab_reduce_kernel.
+template <bool SPARSE>
+__global__ void __launch_bounds__(256) lbs_backward_joints_kernel(AgLbsArgs a, float* __restrict__ slabs)
+{
+    extern __shared__ float lds[];
+    const int J = a.J;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int first = (blockIdx.x * 4 + wave) * 64;
+    const int rows = max(0, min(64, a.N - first));            // wave-uniform; 0 for the idle waves of the last workgroup
+    float* tile = lds + (size_t)wave * 64 * J;
+    float* gm_rows = lds + (size_t)4 * 64 * J + wave * 64 * 12;
+    float* part = lds + (size_t)4 * 64 * J + 4 * 64 * 12 + (size_t)wave * J * 12;
+    const int n = first + lane;
+    float GM[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) GM[k] = 0.f;
+    if (rows > 0) {
+        float M[12];
+        if constexpr (SPARSE) {
+            for (int i = lane; i < rows * J; i += 64) tile[i] = 0.f;
+            __builtin_amdgcn_wave_barrier();
+            if (lane < rows) {
+                for (int s = 0; s < a.K; s++) {
+                    const int j = a.sp_idx[(size_t)s * a.N + n];
+                    if (j < J) tile[lane * J + j] += a.sp_w[(size_t)s * a.N + n];
+                }
+                blend_matrix_sparse(a.sp_idx, a.sp_w, a.K, a.N, n, a.jnt_mats, M);
+            }
+            __builtin_amdgcn_wave_barrier();
+        } else {
+            stage_rows(a.lbs, a.N, J, first, tile, lane);
+            if (lane < rows) blend_matrix(tile + lane * J, a.jnt_mats, J, M);
+        }
+        if (lane < rows) lbs_backward_gaussian<true>(a, n, M, nullptr, nullptr, GM);
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) gm_rows[lane * 12 + k] = GM[k];
+    __builtin_amdgcn_wave_barrier();
+    for (int j = lane; j < J; j += 64) {
+        float acc[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) acc[k] = 0.f;
+        for (int r = 0; r < rows; r++) {
+            const float w = tile[r * J + j];
+            const float* g = gm_rows + r * 12;              // wave-uniform address: broadcast
+#pragma unroll
+            for (int k = 0; k < 12; k++) acc[k] = fmaf(w, g[k], acc[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) part[j * 12 + k] = acc[k];
+    }
+    __syncthreads();
+    const float* p0 = lds + (size_t)4 * 64 * J + 4 * 64 * 12;
+    const int JK = J * 12;
+    float* out = slabs + (size_t)blockIdx.x * JK;
+    for (int i = threadIdx.x; i < JK; i += 256) out[i] = ((p0[i] + p0[JK + i]) + p0[2 * JK + i]) + p0[3 * JK + i];
+}
+
+// Joint-matrix gradient, pass 2: dL/dA [J][4][4] = the sum of the slabs, in a fixed order.  A workgroup owns 16 of the J * 12 outputs:
+// thread (group g, output c) sums slabs g, g + 64, g + 128, ... in order, then a fixed tree over the 64 groups.  Row 3 of every
+// matrix is written as 0 (the forward never reads it).
+constexpr int kSlabOuts = 16, kSlabGroups = 64;
+__global__ void __launch_bounds__(kSlabOuts * kSlabGroups) lbs_joint_slab_reduce_kernel(const float* __restrict__ slabs, int nslab, int J,
+                                                                                        float* __restrict__ g_jnt)
+{
+    __shared__ float s_part[kSlabGroups][kSlabOuts + 1];
+    const int c = threadIdx.x % kSlabOuts, g = threadIdx.x / kSlabOuts;
+    const int JK = J * 12;
+    const int o = blockIdx.x * kSlabOuts + c;
+    float acc = 0.f;
+    if (o < JK)
+        for (int s = g; s < nslab; s += kSlabGroups) acc += slabs[(size_t)s * JK + o];
+    s_part[g][c] = acc;
+    __syncthreads();
+    for (int h = kSlabGroups / 2; h > 0; h >>= 1) {
+        if (g < h) s_part[g][c] += s_part[g + h][c];
+        __syncthreads();
+    }
+    if (g == 0 && o < JK) g_jnt[(o / 12) * 16 + o % 12] = s_part[0][c];
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < 4 * J; i += kSlabOuts * kSlabGroups) g_jnt[(i / 4) * 16 + 12 + i % 4] = 0.f;
+}
+
 }  // namespace ag
 
 using namespace ag;
@@ -443,6 +634,47 @@ int ag_lbs_backward(const AgLbsArgs* a, float* g_positions, float* g_rotations, 
         hipLaunchKernelGGL(lbs_backward_kernel<false>, dim3((a->N + 255) / 256), dim3(256), lds, s, *a, g_positions, g_rotations);
     }
     return check_hip(hipGetLastError(), "lbs_backward_kernel");
+}
+
+size_t ag_lbs_backward_joints_workspace_bytes(int32_t N, int32_t J)
+{
+    if (N <= 0 || J <= 0) return 0;
+    return (size_t)((N + 255) / 256) * (size_t)J * 12 * sizeof(float);
+}
+
+int ag_lbs_backward_joints(const AgLbsArgs* a, float* g_positions, float* g_rotations, float* g_jnt_mats, void* workspace,
+                           size_t workspace_bytes, void* stream)
+{
+    int rc = check_lbs(a);
+    if (rc) return rc;
+    if (!g_jnt_mats) { set_error("null joint-matrix gradient output"); return AG_ERR_INVALID_ARGUMENT; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (a->N == 0) return check_hip(hipMemsetAsync(g_jnt_mats, 0, (size_t)a->J * 16 * sizeof(float), s), "memset");
+    if (!workspace || workspace_bytes < ag_lbs_backward_joints_workspace_bytes(a->N, a->J)) {
+        set_error("lbs_backward_joints: workspace too small");
+        return AG_ERR_SCRATCH_TOO_SMALL;
+    }
+    const int nslab = (a->N + 255) / 256;
+    const int lds = (4 * 64 * a->J + 4 * 64 * 12 + 4 * a->J * 12) * (int)sizeof(float);
+    if (lds > 160 * 1024) { set_error("lbs_backward_joints: J = %d needs %d B of LDS (J <= 140)", a->J, lds); return AG_ERR_INVALID_ARGUMENT; }
+    float* slabs = static_cast<float*>(workspace);
+    if (g_positions || g_rotations) {            // the position / rotation gradients: ag_lbs_backward's own launch, bit for bit
+        if (!g_positions || !g_rotations) { set_error("lbs_backward_joints: dL_dpositions and dL_drotations are both set or both NULL"); return AG_ERR_INVALID_ARGUMENT; }
+        if ((rc = ag_lbs_backward(a, g_positions, g_rotations, stream))) return rc;
+    }
+    if (a->K > 0) {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lbs_backward_joints_kernel<true>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        hipLaunchKernelGGL(lbs_backward_joints_kernel<true>, dim3(nslab), dim3(256), lds, s, *a, slabs);
+    } else {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lbs_backward_joints_kernel<false>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        hipLaunchKernelGGL(lbs_backward_joints_kernel<false>, dim3(nslab), dim3(256), lds, s, *a, slabs);
+    }
+    if ((rc = check_hip(hipGetLastError(), "lbs_backward_joints_kernel"))) return rc;
+    hipLaunchKernelGGL(lbs_joint_slab_reduce_kernel, dim3((a->J * 12 + kSlabOuts - 1) / kSlabOuts), dim3(kSlabOuts * kSlabGroups), 0, s,
+                       slabs, nslab, a->J, g_jnt_mats);
+    return check_hip(hipGetLastError(), "lbs_joint_slab_reduce_kernel");
 }
 
 }  // extern "C"

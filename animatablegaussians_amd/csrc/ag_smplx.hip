@@ -286,6 +286,247 @@ __global__ void __launch_bounds__(64) mat4_mul_inverse_kernel(float* __restrict_
         }
 }
 
+// Backward of rodrigues(): R = I + sin(t) K + (1 - cos(t)) K K with t = |rv + 1e-8|, K = skew(rv / t).  dR [9] -> drv [3].
+// The eps keeps the zero pose's gradient finite, as in the reference (its torch autograd of the same expression).
+__device__ __forceinline__ void rodrigues_backward(const float* rv, const float* dR, float* drv)
+{
+    const float e[3] = {rv[0] + 1e-8f, rv[1] + 1e-8f, rv[2] + 1e-8f};
+    const float angle = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+    const float rx = rv[0] / angle, ry = rv[1] / angle, rz = rv[2] / angle;
+    const float s = sinf(angle), co = cosf(angle), c1 = 1.f - co;
+    const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
+    float ds = 0.f, dc1 = 0.f, dK[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            float kk = 0.f, t = 0.f;
+            for (int k = 0; k < 3; ++k) {
+                kk = fmaf(K[3 * r + k], K[3 * k + c], kk);
+                t += dR[3 * r + k] * K[3 * c + k] + K[3 * k + r] * dR[3 * k + c];     // (dR K^T + K^T dR)[r][c]
+            }
+            ds += dR[3 * r + c] * K[3 * r + c];
+            dc1 += dR[3 * r + c] * kk;
+            dK[3 * r + c] = s * dR[3 * r + c] + c1 * t;
+        }
+    const float da[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
+    // axis = rv / angle;  angle = |e|
+    const float dangle = ds * co + dc1 * s - (da[0] * rv[0] + da[1] * rv[1] + da[2] * rv[2]) / (angle * angle);
+    for (int c = 0; c < 3; ++c) drv[c] = da[c] / angle + dangle * e[c] / angle;
+}
+
+// Reverse of smplx_chain_kernel, one wave per pose: recomputes the rest joints, the local transforms and the global chain, then walks
+// the tree levels from the deepest to the root.  A parent gathers its children's contributions in ascending joint order, so the
+// result does not depend on scheduling.  Inputs dA [B][J][4][4] (row 3 unused) and djoints [B][J][3], either may be NULL.
+// Outputs: dpose [B][J][3]; dtransl [B][3] (NULL: skipped); dcomps [B][NB] through the folded joint_dirs (NULL: skipped).
+__global__ void __launch_bounds__(64) smplx_chain_backward_kernel(float* __restrict__ dpose, float* __restrict__ dtransl,
+                                                                 float* __restrict__ dcomps, const float* __restrict__ dA,
+                                                                 const float* __restrict__ djoints, const float* __restrict__ full_pose,
+                                                                 const float* __restrict__ comps, const float* __restrict__ joint_template,
+                                                                 const float* __restrict__ joint_dirs, const int* __restrict__ parents,
+                                                                 int J, int NB)
+{
+    __shared__ Affine s_glob[kMaxJoints];
+    __shared__ float s_rest[kMaxJoints][3];
+    __shared__ float s_cr[kMaxJoints][9];     // a joint's contribution to its parent's dL/d(global rotation)
+    __shared__ float s_ct[kMaxJoints][3];     // ... to its parent's dL/d(global translation)
+    __shared__ float s_dt[kMaxJoints][3];     // dL/d(local translation) = dL/d(rest_j - rest_parent)
+    __shared__ float s_drest[kMaxJoints][3];
+    __shared__ int s_par[kMaxJoints];
+    __shared__ int s_maxdepth;
+    const int b = blockIdx.x, j = threadIdx.x;
+    const bool on = j < J;
+    if (j == 0) s_maxdepth = 0;
+    __syncthreads();
+
+    // ---- forward recompute (smplx_chain_kernel) ----
+    Affine loc;
+    float rest[3] = {0.f, 0.f, 0.f};
+    int parent = -1, depth = 0;
+    if (on) {
+        for (int c = 0; c < 3; ++c) {
+            const float* d = joint_dirs + (size_t)(3 * j + c) * NB;
+            float acc = 0.f;
+            for (int l = 0; l < NB; ++l) acc = fmaf(d[l], comps[(size_t)b * NB + l], acc);
+            rest[c] = joint_template[3 * j + c] + acc;
+            s_rest[j][c] = rest[c];
+        }
+        parent = parents[j];
+        s_par[j] = parent;
+    }
+    __syncthreads();
+    if (on) {
+        rodrigues(full_pose + ((size_t)b * J + j) * 3, loc.r);
+        for (int c = 0; c < 3; ++c) loc.t[c] = parent >= 0 ? rest[c] - s_rest[parent][c] : rest[c];
+        for (int p = parent; p >= 0; p = s_par[p]) ++depth;
+        atomicMax(&s_maxdepth, depth);
+        if (depth == 0) s_glob[j] = loc;
+    }
+    __syncthreads();
+    const int maxdepth = s_maxdepth;
+    for (int d = 1; d <= maxdepth; ++d) {
+        if (on && depth == d) {
+            const Affine& P = s_glob[parent];
+            Affine g;
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c)
+                    g.r[3 * r + c] = fmaf(P.r[3 * r + 2], loc.r[6 + c], fmaf(P.r[3 * r + 1], loc.r[3 + c], P.r[3 * r] * loc.r[c]));
+                g.t[r] = fmaf(P.r[3 * r + 2], loc.t[2], fmaf(P.r[3 * r + 1], loc.t[1], P.r[3 * r] * loc.t[0])) + P.t[r];
+            }
+            s_glob[j] = g;
+        }
+        __syncthreads();
+    }
+
+    // ---- direct gradients: A_j[:3, :3] = Gr_j;  A_j[:3, 3] = Gt_j - Gr_j rest_j (+ transl);  joints_j = Gt_j (+ transl) ----
+    float dGr[9], dGt[3], drest[3] = {0.f, 0.f, 0.f};
+    if (on) {
+        const float* a = dA ? dA + ((size_t)b * J + j) * 16 : nullptr;
+        const float* dj = djoints ? djoints + ((size_t)b * J + j) * 3 : nullptr;
+        const Affine& g = s_glob[j];
+        for (int r = 0; r < 3; ++r) {
+            const float dcol = a ? a[4 * r + 3] : 0.f;
+            dGt[r] = dcol + (dj ? dj[r] : 0.f);
+            for (int c = 0; c < 3; ++c) {
+                dGr[3 * r + c] = (a ? a[4 * r + c] : 0.f) - dcol * rest[c];
+                drest[c] -= g.r[3 * r + c] * dcol;
+            }
+        }
+        for (int r = 0; r < 3; ++r) s_ct[j][r] = dGt[r];
+    }
+    __syncthreads();
+    if (dtransl && j < 3) {           // body_models.py:1272-1275: transl is added to every A_j[:3, 3] and every joint
+        float acc = 0.f;
+        for (int k = 0; k < J; ++k) acc += s_ct[k][j];
+        dtransl[3 * b + j] = acc;
+    }
+    __syncthreads();
+
+    // ---- the chain in reverse, one tree level per step ----
+    for (int d = maxdepth; d >= 0; --d) {
+        if (on && depth == d) {
+            // Gr_j = Gr_p R_j,  Gt_j = Gr_p t_j + Gt_p   (root: Gr_0 = R_0, Gt_0 = t_0)
+            float dR[9], dt[3];
+            if (parent >= 0) {
+                const Affine& P = s_glob[parent];
+                for (int k = 0; k < 3; ++k) {
+                    for (int c = 0; c < 3; ++c)
+                        dR[3 * k + c] = P.r[k] * dGr[c] + P.r[3 + k] * dGr[3 + c] + P.r[6 + k] * dGr[6 + c];
+                    dt[k] = P.r[k] * dGt[0] + P.r[3 + k] * dGt[1] + P.r[6 + k] * dGt[2];
+                }
+                for (int r = 0; r < 3; ++r) {
+                    for (int k = 0; k < 3; ++k)
+                        s_cr[j][3 * r + k] = dGr[3 * r] * loc.r[3 * k] + dGr[3 * r + 1] * loc.r[3 * k + 1] + dGr[3 * r + 2] * loc.r[3 * k + 2] +
+                                             dGt[r] * loc.t[k];
+                    s_ct[j][r] = dGt[r];
+                }
+            } else {
+                for (int k = 0; k < 9; ++k) dR[k] = dGr[k];
+                for (int k = 0; k < 3; ++k) dt[k] = dGt[k];
+            }
+            for (int k = 0; k < 3; ++k) s_dt[j][k] = dt[k];
+            rodrigues_backward(full_pose + ((size_t)b * J + j) * 3, dR, dpose + ((size_t)b * J + j) * 3);
+        }
+        __syncthreads();
+        if (on && depth == d - 1) {
+            for (int c = j + 1; c < J; ++c)
+                if (s_par[c] == j) {
+                    for (int k = 0; k < 9; ++k) dGr[k] += s_cr[c][k];
+                    for (int k = 0; k < 3; ++k) dGt[k] += s_ct[c][k];
+                }
+        }
+        __syncthreads();
+    }
+
+    // ---- rest joints: t_j = rest_j - rest_parent;  rest_j = joint_template_j + joint_dirs_j . comps ----
+    if (on) {
+        for (int k = 0; k < 3; ++k) drest[k] += s_dt[j][k];
+        for (int c = j + 1; c < J; ++c)
+            if (s_par[c] == j)
+                for (int k = 0; k < 3; ++k) drest[k] -= s_dt[c][k];
+        for (int k = 0; k < 3; ++k) s_drest[j][k] = drest[k];
+    }
+    __syncthreads();
+    if (dcomps)
+        for (int l = j; l < NB; l += 64) {
+            float acc = 0.f;
+            for (int k = 0; k < J; ++k)
+                for (int c = 0; c < 3; ++c) acc = fmaf(s_drest[k][c], joint_dirs[(size_t)(3 * k + c) * NB + l], acc);
+            dcomps[(size_t)b * NB + l] = acc;
+        }
+}
+
+// general 4x4 inverse through the 2x2 minors of the top and bottom row pairs (adjugate / determinant)
+__device__ __forceinline__ void inverse4(const float* m, float* inv)
+{
+    const float s0 = m[0] * m[5] - m[4] * m[1], s1 = m[0] * m[6] - m[4] * m[2], s2 = m[0] * m[7] - m[4] * m[3];
+    const float s3 = m[1] * m[6] - m[5] * m[2], s4 = m[1] * m[7] - m[5] * m[3], s5 = m[2] * m[7] - m[6] * m[3];
+    const float c5 = m[10] * m[15] - m[14] * m[11], c4 = m[9] * m[15] - m[13] * m[11], c3 = m[9] * m[14] - m[13] * m[10];
+    const float c2 = m[8] * m[15] - m[12] * m[11], c1 = m[8] * m[14] - m[12] * m[10], c0 = m[8] * m[13] - m[12] * m[9];
+    const float det = s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
+    const float id = 1.f / det;
+    inv[0] = (m[5] * c5 - m[6] * c4 + m[7] * c3) * id;
+    inv[1] = (-m[1] * c5 + m[2] * c4 - m[3] * c3) * id;
+    inv[2] = (m[13] * s5 - m[14] * s4 + m[15] * s3) * id;
+    inv[3] = (-m[9] * s5 + m[10] * s4 - m[11] * s3) * id;
+    inv[4] = (-m[4] * c5 + m[6] * c2 - m[7] * c1) * id;
+    inv[5] = (m[0] * c5 - m[2] * c2 + m[3] * c1) * id;
+    inv[6] = (-m[12] * s5 + m[14] * s2 - m[15] * s1) * id;
+    inv[7] = (m[8] * s5 - m[10] * s2 + m[11] * s1) * id;
+    inv[8] = (m[4] * c4 - m[5] * c2 + m[7] * c0) * id;
+    inv[9] = (-m[0] * c4 + m[1] * c2 - m[3] * c0) * id;
+    inv[10] = (m[12] * s4 - m[13] * s2 + m[15] * s0) * id;
+    inv[11] = (-m[8] * s4 + m[9] * s2 - m[11] * s0) * id;
+    inv[12] = (-m[4] * c3 + m[5] * c1 - m[6] * c0) * id;
+    inv[13] = (m[0] * c3 - m[1] * c1 + m[2] * c0) * id;
+    inv[14] = (-m[12] * s3 + m[13] * s1 - m[14] * s0) * id;
+    inv[15] = (m[8] * s3 - m[9] * s1 + m[10] * s0) * id;
+}
+
+// Backward of out[i] = a[i] X,  X = inverse(b[i % b_batch]):  da[i] = dout[i] X^T;  db[k] = -X^T (sum_{i % b_batch == k} a[i]^T dout[i]) X^T.
+// One thread per b matrix; it walks its a's in ascending i (fixed order).  da / db may be NULL.
+__global__ void __launch_bounds__(64) mat4_mul_inverse_backward_kernel(float* __restrict__ da, float* __restrict__ db,
+                                                                      const float* __restrict__ dout, const float* __restrict__ a,
+                                                                      const float* __restrict__ bm, int n, int b_batch)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= b_batch) return;
+    float X[16], dX[16];
+    inverse4(bm + (size_t)k * 16, X);
+    for (int e = 0; e < 16; ++e) dX[e] = 0.f;
+    for (int i = k; i < n; i += b_batch) {
+        const float* g = dout + (size_t)i * 16;
+        if (da)
+            for (int r = 0; r < 4; ++r)
+                for (int c = 0; c < 4; ++c) {
+                    float acc = 0.f;
+                    for (int q = 0; q < 4; ++q) acc = fmaf(g[4 * r + q], X[4 * c + q], acc);
+                    da[(size_t)i * 16 + 4 * r + c] = acc;
+                }
+        if (db) {
+            const float* ai = a + (size_t)i * 16;
+            for (int r = 0; r < 4; ++r)
+                for (int c = 0; c < 4; ++c) {
+                    float acc = dX[4 * r + c];
+                    for (int q = 0; q < 4; ++q) acc = fmaf(ai[4 * q + r], g[4 * q + c], acc);
+                    dX[4 * r + c] = acc;
+                }
+        }
+    }
+    if (!db) return;
+    float T[16];   // T = X^T dX
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            float acc = 0.f;
+            for (int q = 0; q < 4; ++q) acc = fmaf(X[4 * q + r], dX[4 * q + c], acc);
+            T[4 * r + c] = acc;
+        }
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            float acc = 0.f;
+            for (int q = 0; q < 4; ++q) acc = fmaf(T[4 * r + q], X[4 * c + q], acc);
+            db[(size_t)k * 16 + 4 * r + c] = -acc;
+        }
+}
+
 static bool model_ok(const AgSmplxModel* m)
 {
     return m && m->V > 0 && m->J > 0 && m->J <= kMaxJoints && m->NB >= 0 && m->NB <= 4096 && m->v_template && m->posedirs &&
@@ -389,6 +630,32 @@ int ag_mat4_mul_inverse(float* out, const float* a, const float* b, int32_t n, i
     if (!out || !a || !b) { set_error("null pointer"); return AG_ERR_INVALID_ARGUMENT; }
     hipLaunchKernelGGL(mat4_mul_inverse_kernel, dim3((n + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), out, a, b, n, b_batch);
     return check_hip(hipGetLastError(), "mat4_mul_inverse_kernel");
+}
+
+int ag_smplx_backward(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* dL_dA,
+                      const float* dL_djoints, float* dL_dfull_pose, float* dL_dtransl, float* dL_dshape_components, void* stream)
+{
+    if (!model_ok(m)) { set_error("smplx_backward: bad model (need 0 < J <= 64, non-null arrays)"); return AG_ERR_INVALID_ARGUMENT; }
+    if (!folded_ok(m)) { set_error("smplx_backward: joint_template / joint_dirs missing -- run ag_smplx_prepare once per model"); return AG_ERR_INVALID_ARGUMENT; }
+    if (B < 0) { set_error("smplx_backward: B < 0"); return AG_ERR_INVALID_ARGUMENT; }
+    if (B == 0) return AG_OK;
+    if (!full_pose || !dL_dfull_pose || (m->NB > 0 && !shape_components)) { set_error("smplx_backward: null pointer"); return AG_ERR_INVALID_ARGUMENT; }
+    hipLaunchKernelGGL(smplx_chain_backward_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), dL_dfull_pose, dL_dtransl,
+                       m->NB > 0 ? dL_dshape_components : nullptr, dL_dA, dL_djoints, full_pose, shape_components, m->joint_template,
+                       m->joint_dirs, m->parents, m->J, m->NB);
+    return check_hip(hipGetLastError(), "smplx_chain_backward_kernel");
+}
+
+int ag_mat4_mul_inverse_backward(float* dL_da, float* dL_db, const float* dL_dout, const float* a, const float* b, int32_t n, int32_t b_batch,
+                                 void* stream)
+{
+    if (n < 0 || b_batch <= 0 || (n > 0 && n % b_batch)) { set_error("mat4_mul_inverse_backward: need n >= 0, b_batch >= 1 dividing n"); return AG_ERR_INVALID_ARGUMENT; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (n == 0) return dL_db ? check_hip(hipMemsetAsync(dL_db, 0, (size_t)b_batch * 16 * sizeof(float), s), "memset") : AG_OK;
+    if (!dL_dout || !b || (dL_db && !a)) { set_error("null pointer"); return AG_ERR_INVALID_ARGUMENT; }
+    if (!dL_da && !dL_db) return AG_OK;
+    hipLaunchKernelGGL(mat4_mul_inverse_backward_kernel, dim3((b_batch + 63) / 64), dim3(64), 0, s, dL_da, dL_db, dL_dout, a, b, n, b_batch);
+    return check_hip(hipGetLastError(), "mat4_mul_inverse_backward_kernel");
 }
 
 int ag_smplx_keypoints(float* out, const float* vertices, const int32_t* idx, const float* w, int32_t B, int32_t V, int32_t K, void* stream)

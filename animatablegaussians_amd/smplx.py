@@ -8,7 +8,11 @@ the constructor and ``forward`` signature of ``smplx/body_models.py:886-1290`` r
 evaluates any batch of poses in ONE pass of ``ag_smplx_forward`` (include/ag_smplx.h): the 61-MB pose-corrective basis is read
 once for the whole batch.  ``data_item`` is the three-call pattern of the dataset as one batch of three + ``ag_mat4_mul_inverse``.
 
-Forward only (the reference calls it under ``torch.no_grad()``, dataset_mv_rgb.py:118); float32; there is no CPU path.
+``forward`` is differentiable, as the reference's torch model is, for the outputs ``A`` and ``joints[:, :55]`` (the kinematic chain:
+``ag_smplx_backward``) with respect to ``betas``, ``expression``, every pose argument and ``transl``; ``mat4_mul_inverse`` is
+differentiable in both operands.  The vertices and the vertex key points ``joints[:, 55:]`` have no backward: a non-zero gradient
+that reaches them raises ``NotImplementedError``.  ``data_item`` (the dataset path) runs without autograd, as the reference's
+dataset does (dataset_mv_rgb.py:118).  float32; there is no CPU path.
 The vertex ids of the 21 extra joints are SMPL-X model-topology constants (smplx/vertex_ids.py:49-72).
 """
 from __future__ import annotations
@@ -68,19 +72,89 @@ class SMPLXOutput:
         return [(k, getattr(self, k)) for k in self.keys()]
 
 
+class _Mat4MulInverse(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = a.contiguous(), b.contiguous()
+        n, nb = a.numel() // 16, b.numel() // 16
+        if nb == 0 or n % nb:
+            raise RuntimeError(f"mat4_mul_inverse: {n} matrices against {nb}")
+        out = torch.empty_like(a)
+        with torch.cuda.device(a.device):
+            _lib.check(_lib.lib().ag_mat4_mul_inverse(_p(out), _p(a), _p(b), n, nb, _stream(a.device)), "ag_mat4_mul_inverse")
+        ctx.save_for_backward(a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        n, nb = a.numel() // 16, b.numel() // 16
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        g = g.contiguous()
+        with torch.cuda.device(a.device):
+            _lib.check(_lib.lib().ag_mat4_mul_inverse_backward(_p(da), _p(db), _p(g), _p(a), _p(b), n, nb, _stream(a.device)),
+                       "ag_mat4_mul_inverse_backward")
+        return da, db
+
+
 def mat4_mul_inverse(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """``a @ inverse(b)`` for 4x4 matrices, ``b`` broadcast over the leading dimension of ``a`` when it has fewer matrices
-    (dataset_mv_rgb.py:170-171)."""
+    (dataset_mv_rgb.py:170-171).  Differentiable in both operands (``ag_mat4_mul_inverse_backward``)."""
     if a.shape[-2:] != (4, 4) or b.shape[-2:] != (4, 4) or not a.is_cuda or a.dtype != torch.float32 or b.dtype != torch.float32:
         raise RuntimeError("mat4_mul_inverse: float32 GPU tensors [..., 4, 4]")
-    a, b = a.contiguous(), b.contiguous()
-    n, nb = a.numel() // 16, b.numel() // 16
-    if nb == 0 or n % nb:
-        raise RuntimeError(f"mat4_mul_inverse: {n} matrices against {nb}")
-    out = torch.empty_like(a)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.lib().ag_mat4_mul_inverse(_p(out), _p(a), _p(b), n, nb, _stream(a.device)), "ag_mat4_mul_inverse")
-    return out
+    return _Mat4MulInverse.apply(a, b)
+
+
+class _SmplxLbs(torch.autograd.Function):
+    """(shape components, full pose, transl) -> (vertices, joints [B,J,3], A); backward for joints and A only (ag_smplx_backward)."""
+
+    @staticmethod
+    def forward(ctx, model, comps, pose, transl):
+        ctx.set_materialize_grads(False)
+        verts, joints, A = model._lbs_launch(comps, pose, transl)
+        ctx.model, ctx.has_transl = model, transl is not None
+        ctx.save_for_backward(comps, pose)
+        return verts, joints, A
+
+    @staticmethod
+    def backward(ctx, g_verts, g_joints, g_A):
+        if g_verts is not None and bool(g_verts.ne(0).any()):
+            raise NotImplementedError("SMPLX: the vertices have no backward (only A and joints[:, :55], the kinematic chain, do)")
+        comps, pose = ctx.saved_tensors
+        model = ctx.model
+        m = model._model()
+        B, dev = pose.shape[0], pose.device
+        dpose = torch.empty_like(pose)
+        dcomps = torch.empty_like(comps) if m.NB > 0 else None
+        dtr = torch.empty((B, 3), dtype=torch.float32, device=dev) if ctx.has_transl and ctx.needs_input_grad[3] else None
+        gA = g_A.contiguous() if g_A is not None else None
+        gJ = g_joints.contiguous() if g_joints is not None else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ag_smplx_backward(ctypes.byref(m), B, _p(comps), _p(pose), _p(gA), _p(gJ), _p(dpose), _p(dtr), _p(dcomps),
+                                                    _stream(dev)), "ag_smplx_backward")
+        return None, dcomps, dpose, dtr
+
+
+class _Keypoints(torch.autograd.Function):
+    """The barycentric vertex key points (ag_smplx_keypoints); no backward: a non-zero gradient that reaches them raises."""
+
+    @staticmethod
+    def forward(ctx, model, verts):
+        ctx.set_materialize_grads(False)
+        B, dev = verts.shape[0], verts.device
+        K = model._kp_idx.shape[0]
+        extra = torch.empty((B, K, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ag_smplx_keypoints(_p(extra), _p(verts), _p(model._kp_idx), _p(model._kp_w), B, verts.shape[1], K,
+                                                     _stream(dev)), "ag_smplx_keypoints")
+        return extra
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is not None and bool(g.ne(0).any()):
+            raise NotImplementedError("SMPLX: the vertex key points joints[:, 55:] (extra vertex joints and face landmarks) have no backward")
+        return None, None
 
 
 class SMPLX(nn.Module):
@@ -199,7 +273,8 @@ class SMPLX(nn.Module):
         return self._desc[1]
 
     def lbs(self, shape_components: torch.Tensor, full_pose: torch.Tensor, transl: Optional[torch.Tensor]):
-        """(vertices [B,V,3], posed joints [B,J,3], A [B,J,4,4]) of smplx/lbs.py:152-246 (+ body_models.py:1272-1275)."""
+        """(vertices [B,V,3], posed joints [B,J,3], A [B,J,4,4]) of smplx/lbs.py:152-246 (+ body_models.py:1272-1275).
+        Differentiable for joints and A (``_SmplxLbs``)."""
         dev = self.v_template.device
         m = self._model()
         B = full_pose.shape[0]
@@ -208,6 +283,12 @@ class SMPLX(nn.Module):
         tr = None if transl is None else transl.to(dev, torch.float32).reshape(B, 3).contiguous()
         if comps.shape != (B, m.NB):
             raise RuntimeError(f"shape components {tuple(comps.shape)} != ({B}, {m.NB})")
+        return _SmplxLbs.apply(self, comps, pose, tr)
+
+    def _lbs_launch(self, comps, pose, tr):
+        dev = self.v_template.device
+        m = self._model()
+        B = pose.shape[0]
         verts = torch.empty((B, m.V, 3), dtype=torch.float32, device=dev)
         joints = torch.empty((B, m.J, 3), dtype=torch.float32, device=dev)
         A = torch.empty((B, m.J, 4, 4), dtype=torch.float32, device=dev)
@@ -247,12 +328,7 @@ class SMPLX(nn.Module):
         if transl is not None and transl.shape[0] != B:
             transl = transl.expand(B, -1)
         verts, joints, A = self.lbs(comps, full_pose, transl)
-        K = self._kp_idx.shape[0]
-        extra = torch.empty((B, K, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ag_smplx_keypoints(_p(extra), _p(verts), _p(self._kp_idx), _p(self._kp_w), B, verts.shape[1], K,
-                                                     _stream(dev)), "ag_smplx_keypoints")
-        joints = torch.cat([joints, extra], 1)
+        joints = torch.cat([joints, _Keypoints.apply(self, verts)], 1)
         v_shaped = None
         if return_shaped:                                                              # body_models.py:1277-1279 (betas only)
             only_betas = torch.cat([betas, torch.zeros_like(expression)], -1).contiguous()
@@ -265,6 +341,7 @@ class SMPLX(nn.Module):
                            right_hand_pose=right_hand_pose, jaw_pose=jaw_pose, v_shaped=v_shaped, transl=transl,
                            full_pose=full_pose if return_full_pose else None, A=A)
 
+    @torch.no_grad()
     def data_item(self, smpl_data, pose_idx: int, cano_global_orient, cano_transl, cano_body_pose) -> dict:
         """dataset/dataset_mv_rgb.py:118-143,155-171 for one frame: the live, canonical and live-without-root evaluations as ONE
         batch of three, then both `cano2live` matrix sets.  `smpl_data`: the tensors / arrays of smpl_params.npz (host memory,

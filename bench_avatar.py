@@ -463,6 +463,57 @@ def full_step_probe(dev, block=4, blocks=5):
     return out
 
 
+def pose_grad_bench(dev, steps, warmup):
+    """ms per pose-refinement iteration: SMPL-X (live and without root) -> mat4_mul_inverse -> get_pose_map -> render -> L1 image loss
+    -> backward to body_pose -> Adam.  Eval mode, every network weight frozen (only the input gradients of the StyleUNets run), the
+    synthetic subject and synthetic SMPL-X model (J = 55), one 1024^2 view."""
+    import numpy as np
+    import torch
+    from animatablegaussians_amd import camera, synth
+    from animatablegaussians_amd.avatar import AvatarNet
+    from animatablegaussians_amd.smplx import SMPLX, mat4_mul_inverse
+    torch.manual_seed(31359)
+    net = AvatarNet.synthetic({'with_viewdirs': True}, device=dev)
+    net.eval()
+    for p in net.parameters():
+        p.requires_grad_(False)
+    smplx = SMPLX(synth.smplx_model_arrays(), gender='neutral', use_pca=False, flat_hand_mean=True, device=dev)
+    S = 1024
+    extr = torch.from_numpy(camera.calc_front_mv(np.zeros(3, np.float32), tar_pos=(0.0, 0.0, 2.5))).to(dev)
+    intr = torch.tensor([[1100.0, 0, S / 2], [0, 1100.0, S / 2], [0, 0, 1]], device=dev)
+    go = torch.tensor([[0.05, 0.0, 0.0]], device=dev)
+    with torch.no_grad():
+        cano = smplx(body_pose=torch.zeros(1, 63, device=dev)).A[0]
+
+    def items_of(bp):
+        live, woroot = smplx(body_pose=bp, global_orient=go), smplx(body_pose=bp)
+        c2l = mat4_mul_inverse(torch.stack([live.A[0], woroot.A[0]]), cano)
+        return {'cano2live_jnt_mats': c2l[0], 'cano2live_jnt_mats_woRoot': c2l[1], 'extr': extr, 'intr': intr, 'img_w': S, 'img_h': S}
+
+    theta = torch.randn(1, 63, generator=torch.Generator().manual_seed(0)).to(dev) * 0.1
+    with torch.no_grad():
+        it = items_of(theta)
+        net.get_pose_map(it)
+        target = net.render(it)['rgb_map'].clone()
+    bp = (theta + 0.05).requires_grad_(True)
+    opt = torch.optim.Adam([bp], lr=0.002)
+    losses = []
+
+    def step(_i):
+        opt.zero_grad(set_to_none=True)
+        it = items_of(bp)
+        net.get_pose_map(it)
+        loss = (net.render(it)['rgb_map'] - target).abs().mean()
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+
+    ms = timed_median(step, steps, warmup, dev)
+    return {"metric": "pose refinement iteration (SMPL-X + pose map + render + L1 + backward to body_pose + Adam) ms @1024^2",
+            "ms_per_iter": ms, "gaussians": int(net.lbs.shape[0]), "steps": steps, "warmup": warmup,
+            "loss_first": float(losses[0]), "loss_last": float(losses[-1])}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -478,6 +529,8 @@ def main() -> None:
     ap.add_argument("--conv-roofline", action="store_true", help="only print the in-run MFMA roofline of the convolution kernels")
     ap.add_argument("--pose-per-rank", action="store_true", help="N > 1: every rank trains on its own pose (x --views cameras of it) instead of sharding the "
                     "views of one pose: no pose-shared work is replicated, the job scales weakly (DESIGN.md section 6, mode (b))")
+    ap.add_argument("--pose-grad", action="store_true", help="only time test-time pose refinement: SMPL-X -> mat4_mul_inverse -> get_pose_map -> "
+                    "render -> L1 -> backward -> Adam on body_pose (eval mode, frozen weights, synthetic subject, 1024^2)")
     args = ap.parse_args()
 
     import torch
@@ -495,6 +548,9 @@ def main() -> None:
     torch.cuda.set_device(dev)
     if args.conv_roofline:
         print(json.dumps({"roofline_mfma": conv_roofline(dev)}), flush=True)
+        return
+    if args.pose_grad:
+        print(json.dumps(pose_grad_bench(dev, args.steps, args.warmup)), flush=True)
         return
 
     ts = TrainingStep(dev, viewdirs=not args.no_viewdirs, lpips=args.lpips and not args.infer, world=world, rank=rank, pose_per_rank=args.pose_per_rank)

@@ -87,6 +87,20 @@ int ag_lbs_backward(const AgLbsArgs* fwd_inputs_and_grads, float* dL_dpositions 
                     void* stream);
 
 /*
+ * The backward with the gradient to the joint matrices as well: dL/d jnt_mats [J,4,4], with dL/dA_j[:3, :4] = sum_n w_nj G_n,
+ * G_n = dL/dM_n (3x4) = g_p (x) [p, 1]  +  [dL/dR_live R_cano^T | 0], and row 3 exactly 0 (the forward never reads it).
+ * dL_dpositions / dL_drotations: both NULL (the pose-map path needs only the joint gradient) or both set, and then written by
+ * ag_lbs_backward's own launch, so they are its bits; the joint gradient is a second pass over the Gaussians.  The sum over them is
+ * deterministic (per-workgroup slabs in `workspace`, combined in a fixed order by a second launch, no float atomics), and the sparse
+ * form gives the dense form's bits: a skipped term is + 0 * G_n.  workspace: device memory of at least
+ * ag_lbs_backward_joints_workspace_bytes(N, J) bytes.  Dense and sparse rows: J <= 140 (LDS).
+ */
+size_t ag_lbs_backward_joints_workspace_bytes(int32_t N, int32_t J);
+int ag_lbs_backward_joints(const AgLbsArgs* fwd_inputs_and_grads, float* dL_dpositions /*[N,3] or NULL*/,
+                           float* dL_drotations /*[N,4] or NULL*/, float* dL_djnt_mats /*[J,4,4]*/, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/*
  * Eval-time hand fusion (network/avatar.py:183-200): inside the bounding boxes of the canonical MANO hands the
  * predicted Gaussians are cross-faded into those of one fixed "mean hands" frame (AvatarNet.generate_mean_hands, :52-77).
  * Per Gaussian, with n_l / n_r = first coordinate of utils/geo_util.py:104-114 normalize_vert_bbox(hand verts, attris = xyz,

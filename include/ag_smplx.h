@@ -62,6 +62,16 @@ size_t ag_smplx_workspace_floats(const AgSmplxModel* m, int32_t B);
 int ag_smplx_forward(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* transl,
                      float* vertices, float* joints, float* A, float* workspace, size_t workspace_floats, void* stream);
 
+/*
+ * Backward of ag_smplx_forward for its outputs A and joints (the kinematic chain; the vertices and the vertex key points have no
+ * backward here).  dL_dA [B][J][4][4] (as returned, transl included; row 3 is not read) and dL_djoints [B][J][3]: either may be NULL
+ * (no gradient).  Writes dL_dfull_pose [B][J][3] (Rodrigues with the reference's `+ 1e-8` inside the norm, so the zero pose has its
+ * finite gradient), dL_dtransl [B][3] when not NULL (the gradient is the same whether or not the forward had a transl), and
+ * dL_dshape_components [B][NB] when NB > 0, through the folded joint_dirs of ag_smplx_prepare.  One wave per pose; deterministic.
+ */
+int ag_smplx_backward(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* dL_dA,
+                      const float* dL_djoints, float* dL_dfull_pose, float* dL_dtransl, float* dL_dshape_components, void* stream);
+
 /* v_shaped [B][V][3] = v_template + shapedirs . shape_components alone (body_models.py:1277-1279 `return_shaped`, where the
  * reference passes the betas without the expression: the caller zeroes those components). */
 int ag_smplx_shape(const AgSmplxModel* m, int32_t B, const float* shape_components, float* v_shaped, void* stream);
@@ -69,6 +79,10 @@ int ag_smplx_shape(const AgSmplxModel* m, int32_t B, const float* shape_componen
 /* out[i] = a[i] @ inverse(b[i % b_batch]) for n row-major 4x4 matrices (dataset_mv_rgb.py:170-171: cano2live_jnt_mats =
  * live.A @ inv(cano.A), and the same canonical matrices again for the pose without root: n = 2 J, b_batch = J). */
 int ag_mat4_mul_inverse(float* out, const float* a, const float* b, int32_t n, int32_t b_batch, void* stream);
+/* Its backward: dL_da[i] = dL_dout[i] inverse(b)^T;  dL_db[k] = -inverse(b_k)^T (sum over i % b_batch == k of a[i]^T dL_dout[i]) inverse(b_k)^T,
+ * summed in ascending i.  Either output may be NULL (not computed); n must be a multiple of b_batch. */
+int ag_mat4_mul_inverse_backward(float* dL_da, float* dL_db, const float* dL_dout, const float* a, const float* b, int32_t n, int32_t b_batch,
+                                 void* stream);
 
 /* Barycentric key points (vertex picks and face landmarks: vertex_joint_selector.py:72-76, lbs.py:108-149):
  * out[b][k] = sum_t w[k][t] * vertices[b][idx[k][t]], t < 3.  idx [K][3] int32, w [K][3]. */
