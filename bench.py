@@ -1,8 +1,11 @@
 #!/usr/bin/env python
 """Headline benchmark: rendered views/sec (forward + backward) at 1024x1024 over ~250 k Gaussians.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the result line: `value`, `ms_per_step`
+and what describes the workload (`config`).  Everything else the benchmark measures or checks runs with --full only.
 
 Workload = BASELINE.json configs[1] ("avatarrex_zzr: 512^2 front/back maps (~250k Gaussians), 1 view @1024^2,
 1xMI355X fwd+bwd"), synthetic: animatablegaussians_amd.synth.avatar_map_gaussians() (268 348 Gaussians on the
@@ -13,13 +16,16 @@ is the library-owned step (rasterizer.FusedRasterStep: one native call per view,
 views rotate over its three internal HIP streams (--streams), as a multi-view trainer issues them: views are independent,
 and the one host synchronisation per view (the reference's num_rendered read-back) overlaps the other view's kernels.  The
 same workload through the reference's operator surface (GaussianRasterizer + public torch.autograd.backward) and on ONE stream
-with ordered steps is timed next to it (`operator_path`, `sequential`).
+with ordered steps is timed next to it under --full (`operator_path`, `sequential`).
 
 Multi-GPU: views are sharded over ranks (weak scaling: every rank renders K views of the same Gaussians).  The
 exchange step of view-sharded rendering is the sum over views of the per-Gaussian attribute gradients (14 floats per
-Gaussian, 15 MB) -- one RCCL all-reduce per step, issued on a side stream and overlapped with the next view.
+Gaussian, 15 MB) -- one RCCL all-reduce per step, issued on a side stream and overlapped with the next view.  With --full, one more
+untimed iteration checks the exchange by linearity (`exchange_check`) and the all-reduce of the three networks' gradients is timed on
+its own (`exchange_styleunet`).
 
-The JSON line also carries
+With --full the JSON line also carries
+  value_blocks : the same number of steps five more times, each block timed like the headline region;
   roofline     : dominant kernel (blend backward), ALGORITHMIC bytes/launch (8T + 44R + 28WH + 40P)
                  / its HIP-event duration measured live in the timed region, against 8 TB/s HBM3E;
   cpu_baseline : the CPU oracle (a restatement of the reference's CUDA kernels -- the reference has no CPU
@@ -58,8 +64,12 @@ def main() -> None:
     ap.add_argument("--prewarm", type=int, default=300, help="untimed steps BEFORE the --warmup steps (clocks, allocator pools, the "
                     "binning capacity of every camera): with the driver's --warmup 5 --steps 20 the timed region is 3 ms long and read 5050 "
                     "views/s where the five blocks after it read 6860-7220 (profiles/r04_bench_driver_cmd.json); not part of the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle timing (profiling runs)")
-    ap.add_argument("--breakdown", action="store_true", help="add a per-kernel HIP-event breakdown pass")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other leg of the benchmark: the stability blocks, "
+                    "the rooflines and the per-kernel breakdown, the one-stream and operator-path rates, the N > 1 exchange check and "
+                    "timing, the whole training step, the 1 M-Gaussian stress size and the CPU baselines (the --no-* options below "
+                    "leave some of them out).  Off: the run does only what `value` needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle timing (profiling runs)")
+    ap.add_argument("--breakdown", action="store_true", help="--full: add a per-kernel HIP-event breakdown pass")
     ap.add_argument("--streams", type=int, default=3, help="render consecutive views round-robin on this many HIP streams: "
                     "the host-side wait for a view's instance count (the reference's num_rendered read-back) overlaps the kernels "
                     "of the previous views, and the latency-bound stages of one view fill the gaps of another.  Library-owned step, "
@@ -71,9 +81,9 @@ def main() -> None:
                     "backward nodes run on the calling thread)")
     ap.add_argument("--operator-path", action="store_true", help="time GaussianRasterizer + torch.autograd.backward (the reference's "
                     "operator surface) in the headline loop instead of the library-owned forward+backward step")
-    ap.add_argument("--no-full-step", action="store_true", help="skip the full_step / roofline_mfma legs (BASELINE configs[2]: the whole "
+    ap.add_argument("--no-full-step", action="store_true", help="--full: skip the full_step / roofline_mfma legs (BASELINE configs[2]: the whole "
                     "training iteration with the three StyleUNets, ~15 s) -- profiling runs of the rasterizer")
-    ap.add_argument("--no-stress", action="store_true", help="skip the stress_1m_2048 leg (BASELINE configs[4] on one GPU, ~3 s)")
+    ap.add_argument("--no-stress", action="store_true", help="--full: skip the stress_1m_2048 leg (BASELINE configs[4] on one GPU, ~3 s)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what its LAST step computed -- the "
                     "view's colour, depth and alpha images, the radii and the per-Gaussian gradients a caller receives -- as DIR/<name>.npy "
                     "(float32; rank 0 at N > 1): the inputs are seeded, so two builds can be compared output for output -- the images and radii "
@@ -82,6 +92,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.cpu_worker:                                    # child process of a cpu_baseline_* leg (no GPU work)
         return {"lbs": _cpu_lbs_worker, "styleunet": _cpu_styleunet_worker}[args.cpu_worker]()
+    if args.breakdown and not args.full:
+        ap.error("--breakdown is a leg of --full")
 
     import numpy as np
     import torch
@@ -243,6 +255,46 @@ def main() -> None:
     if args.dump_outputs and rank == 0 and last is not None:
         # copied now: the next steps reuse the slot's images
         dumped = dump_outputs(args.dump_outputs, last, (args.warmup + args.steps - 1) * world % len(settings))
+    if world > 1:
+        tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+    value = args.gpus * args.steps / elapsed
+    ms_per_step = 1e3 * elapsed / args.steps
+    T_tiles = ((W + 15) // 16) * ((H + 15) // 16)
+    out = {
+        "metric": "rendered views/sec (fwd+bwd) @1024^2, ~250k Gaussians",
+        "value": round(value, 2), "unit": "views/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {
+            "workload": "BASELINE configs[1]: avatar front|back map, 1 view @1024x1024 per step, rasterizer fwd+bwd "
+                        + ("through GaussianRasterizer + torch.autograd" if args.operator_path else
+                           "through the library-owned step (ag_raster_forward_backward, one native call per view; per-camera argument structures and "
+                           "output images prepared once, FusedRasterStep.prepare / run)"),
+            "gaussians": P, "tiles": T_tiles, "views": len(settings), "streams": args.streams,
+            "prewarm": max(0, args.prewarm),      # untimed steps BEFORE the --warmup steps (round 4: the first region of a process is cold)
+            "parallelism": "1 process" if world == 1 else
+                           f"view-sharded x{world}: every rank renders its own view per step and sums its views' per-Gaussian gradients (14 f32 each, "
+                           f"{P * 14 * 4 / 1e6:.1f} MB) on the device; one RCCL all-reduce of the sums per {exch_every} steps of a rank "
+                           f"(= a {exch_every * world}-view iteration), on a communication stream under the next views' kernels",
+            "exchange_every_steps": exch_every if world > 1 else None,
+            "backend": None if world == 1 else (backend if backend == "nccl" else f"{backend}: fewer GPUs than ranks, ranks share devices -- a "
+                                                "functional run of the N > 1 control flow, NOT a measurement"),
+        },
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if not args.full:
+        # a plain run ends with its headline: every leg below is --full's
+        if rank == 0:
+            out["headline"] = headline_of(out)
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # stability evidence for short timed regions (the driver's --steps 20 is a 3-ms region that includes the fill and drain of the
     # stream pipeline): the same number of steps again, five more times, each block timed like the region above
     value_blocks = []
@@ -257,10 +309,6 @@ def main() -> None:
         tbk = torch.tensor(value_blocks, device=dev, dtype=torch.float64)
         dist.all_reduce(tbk, op=dist.ReduceOp.MAX)
         value_blocks = [float(x) for x in tbk.tolist()]
-    if world > 1:
-        tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
 
     # N > 1, untimed: one more iteration with the all-reduce held back, checked by linearity (a checksum of checksums): the rank's
     # accumulator must hold the sum of what its steps packed, and after the all-reduce every rank must hold the same buffer whose
@@ -393,14 +441,11 @@ def main() -> None:
             dist.destroy_process_group()
         return
 
-    T_tiles = ((W + 15) // 16) * ((H + 15) // 16)
     n_dom, ms_dom = prof["blend_backward_kernel"]
     dom_us = 1e3 * ms_dom / max(n_dom, 1)
     alg_dom = 8 * T_tiles + 44 * R_mean + 28 * W * H + 40 * P          # bytes per launch (bwd blend)
     alg_step = 392 * P + 132 * R_mean + 52 * W * H + 24 * T_tiles       # whole raster fwd+bwd
     achieved = alg_dom / (dom_us * 1e-6) / 1e9 if dom_us > 0 else 0.0
-    value = args.gpus * args.steps / elapsed
-    ms_per_step = 1e3 * elapsed / args.steps
 
     # HBM traffic of the dominant kernel comes from PMC counters, which cannot be read from inside this process: the separate
     # rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes over the same workload are summarised in profiles/traffic_head.json
@@ -452,29 +497,11 @@ def main() -> None:
                 "note": "GaussianRasterizer (autograd.Function) forward + torch.autograd.backward with explicit image gradients, same "
                         "kernels; the difference to `value` is host time of the autograd machinery"}
 
-    out = {
-        "metric": "rendered views/sec (fwd+bwd) @1024^2, ~250k Gaussians",
-        "value": round(value, 2), "unit": "views/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
+    out["config"]["instances_per_view"] = int(R_mean)
+    out.update({
         "value_blocks": {"views_per_s": [round(args.gpus * args.steps / t, 1) for t in value_blocks],
                          "note": f"five more blocks of {args.steps} steps right after the timed region, each timed the same way (max over ranks): "
                                  "how far `value` moves from block to block at this region length"},
-        "config": {
-            "workload": "BASELINE configs[1]: avatar front|back map, 1 view @1024x1024 per step, rasterizer fwd+bwd "
-                        + ("through GaussianRasterizer + torch.autograd" if args.operator_path else
-                           "through the library-owned step (ag_raster_forward_backward, one native call per view; per-camera argument structures and "
-                           "output images prepared once, FusedRasterStep.prepare / run)"),
-            "gaussians": P, "instances_per_view": int(R_mean), "tiles": T_tiles, "views": len(settings), "streams": args.streams,
-            "prewarm": max(0, args.prewarm),      # untimed steps BEFORE the --warmup steps (round 4: the first region of a process is cold)
-            "parallelism": "1 process" if world == 1 else
-                           f"view-sharded x{world}: every rank renders its own view per step and sums its views' per-Gaussian gradients (14 f32 each, "
-                           f"{P * 14 * 4 / 1e6:.1f} MB) on the device; one RCCL all-reduce of the sums per {exch_every} steps of a rank "
-                           f"(= a {exch_every * world}-view iteration), on a communication stream under the next views' kernels",
-            "exchange_every_steps": exch_every if world > 1 else None,
-            "backend": None if world == 1 else (backend if backend == "nccl" else f"{backend}: fewer GPUs than ranks, ranks share devices -- a "
-                                                "functional run of the N > 1 control flow, NOT a measurement"),
-        },
         "roofline": {
             "kernel": "blend_backward_wave_kernel",
             "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
@@ -484,7 +511,7 @@ def main() -> None:
             "note": "VALU/LDS/atomic-bound kernel reported against HBM as SURVEY.md 8(d) prescribes; `valu` = the yardstick that fits it",
             "valu": valu_roofline(pairs_mean, dom_us, "backward"),
         },
-    }
+    })
     if breakdown is not None:
         # algorithmic bytes per launch of every raster kernel (DESIGN.md section 4 / SURVEY.md 8d) against its one-stream duration
         alg = {"preprocess_kernel": 112 * P, "tile_scan_kernel": 8 * T_tiles, "scatter_kernel": 20 * P + 12 * R_mean,
@@ -554,8 +581,6 @@ def main() -> None:
         out["exchange_styleunet"] = exchange_leg
     if exchange_check is not None:
         out["exchange_check"] = exchange_check
-    if dumped is not None:
-        out["dumped_outputs"] = dumped
     if world == 1 and not args.no_full_step:
         # BASELINE configs[2] and the MFMA roofline north_star asks for, measured in this process (about 15 s): the whole training
         # iteration at the reference's batch shape (1 view per step) and at 4 views of one pose per step, and the convolution kernels'
@@ -629,15 +654,16 @@ def valu_roofline(pairs: float, us: float, which: str):
 def headline_of(out):
     """The numbers a reader of the LAST 2000 characters of the line needs (the driver keeps that much): short keys, no notes."""
     h = {"value_views_per_s": out["value"], "n_gpus": out["n_gpus"]}
-    r = out.get("roofline", {})
-    h["bwd_us_overlapped"] = r.get("avg_launch_us")
-    h["bwd_frac_hbm"] = r.get("frac")
-    h["bwd_us_one_stream"] = r.get("avg_launch_us_one_stream")
-    h["bwd_frac_hbm_one_stream"] = r.get("frac_one_stream")
-    v = r.get("valu_one_stream") or r.get("valu")
-    if v:
-        h["bwd_G_pair_evals_per_s"] = v["G_pair_evals_per_s"]
-        h["bwd_frac_valu"] = v["frac"]
+    r = out.get("roofline")
+    if r:
+        h["bwd_us_overlapped"] = r.get("avg_launch_us")
+        h["bwd_frac_hbm"] = r.get("frac")
+        h["bwd_us_one_stream"] = r.get("avg_launch_us_one_stream")
+        h["bwd_frac_hbm_one_stream"] = r.get("frac_one_stream")
+        v = r.get("valu_one_stream") or r.get("valu")
+        if v:
+            h["bwd_G_pair_evals_per_s"] = v["G_pair_evals_per_s"]
+            h["bwd_frac_valu"] = v["frac"]
     rk = out.get("roofline_raster_kernels")
     if rk:
         h["raster_one_stream_sum_us"] = rk.get("one_stream_sum_us")

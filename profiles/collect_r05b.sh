@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 O=$R/gpurun_out/r05y
 mkdir -p $O
 # 1. the driver's default command, and the driver's round-end command (--steps 20 --warmup 5)
-( time python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time
-python bench.py --steps 20 --warmup 5 --no-full-step --no-cpu-baseline --no-stress > $O/bench_driver_cmd.json 2> /dev/null
+( time python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time
+python bench.py --full --steps 20 --warmup 5 --no-full-step --no-cpu-baseline --no-stress > $O/bench_driver_cmd.json 2> /dev/null
 # 2. rocprofv3 kernel summary of the raster legs of the same command
 rm -rf /tmp/prof_bench
 ( cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -o b -- python $R/bench.py --no-full-step --no-cpu-baseline --no-stress > $O/bench_profiled.json 2> /dev/null )

@@ -6,9 +6,9 @@ export TMPDIR=/tmp
 O=$R/gpurun_out/r06z
 mkdir -p $O
 # 1. the driver's round-end command with every leg (its last 2000 characters = what the driver's record keeps), and the default command
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 tail -c 2000 $O/bench_driver_cmd.json > $O/bench_driver_cmd_tail2000.txt
-( time python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time
+( time python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time
 # 2. rocprofv3 kernel summary of the raster legs of the same command
 rm -rf /tmp/prof_bench
 ( cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -o b -- python $R/bench.py --no-full-step --no-cpu-baseline --no-stress > $O/bench_profiled.json 2> /dev/null )

@@ -6,5 +6,5 @@ pick='import json,sys; d=json.loads(sys.stdin.readline()); r=d["roofline_raster_
 for rep in 1 2; do
 for v in "$@"; do
   if [ "$v" = head ]; then unset AG_LIB_PATH; else export AG_LIB_PATH=$PWD/profiles/ub/ko/libag_$v.so; fi
-  python bench.py --no-full-step --no-cpu-baseline --no-stress 2> /dev/null | python -c "$pick" "$v rep$rep" | tee -a $O/ab_libs.txt
+  python bench.py --full --no-full-step --no-cpu-baseline --no-stress 2> /dev/null | python -c "$pick" "$v rep$rep" | tee -a $O/ab_libs.txt
 done; done

@@ -3,7 +3,7 @@ timeout 900 python -m pytest tests/test_raster_gpu.py -x -q -m gpu 2>&1 | tail -
 python profiles/fwd_step_stats.py 0 2 5 > $out/fwd_stats_tight.txt 2>&1; AG_LIB_PATH=$PWD/profiles/ub/ko/libag_fstatsdisc.so python profiles/fwd_step_stats.py 0 2 5 > $out/fwd_stats_disc.txt 2>&1
 cat $out/fwd_stats_tight.txt $out/fwd_stats_disc.txt
 run() { label=$1; shift
-  env "$@" timeout 200 python bench.py --steps 400 --warmup 100 --no-cpu-baseline --no-full-step --no-stress > $out/bench_$label.json 2> $out/bench_$label.err
+  env "$@" timeout 200 python bench.py --full --steps 400 --warmup 100 --no-cpu-baseline --no-full-step --no-stress > $out/bench_$label.json 2> $out/bench_$label.err
   python - "$out" "$label" <<'PY'
 import json, sys
 d=json.loads(open(f"{sys.argv[1]}/bench_{sys.argv[2]}.json").read().strip().splitlines()[-1])

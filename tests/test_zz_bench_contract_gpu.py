@@ -8,11 +8,12 @@ import sys
 import pytest
 
 pytestmark = pytest.mark.gpu
+# the legs beyond the headline (rooflines, full_step, stress, CPU baselines, the N > 1 exchange records) run under --full only
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "20"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "20", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -86,6 +87,38 @@ def test_bench_json_line():
     assert 1.0 < lp["views_per_s_1view_per_step"] <= f["views_per_s_1view_per_step"] * 1.1
 
 
+HEADLINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                 "data", "config", "headline"}
+
+
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """Without --full the run sets up, warms up, times its steps, writes --dump-outputs and prints the line: the headline fields with the
+    same meaning as under --full, and none of the other legs."""
+    dump = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "20", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert set(d) == HEADLINE_KEYS | {"dumped_outputs"}, sorted(d)
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
+                 ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict)):
+        assert isinstance(d[k], t), (k, d[k])
+    assert d["metric"] == "rendered views/sec (fwd+bwd) @1024^2, ~250k Gaussians" and d["higher_is_better"] is True
+    assert d["vs_baseline"] is None and d["n_gpus"] == 1 and d["steps"] == 60 and d["warmup"] == 20 and d["scaling"] == "weak"
+    assert d["unit"] == "views/s" and d["dtype"] == "f32" and d["data"] == "synthetic" and "library-owned step" in d["config"]["workload"]
+    assert abs(d["value"] * d["ms_per_step"] - 1000.0) < 5.0                       # value = steps / elapsed at N = 1
+    assert d["headline"] == {"value_views_per_s": d["value"], "n_gpus": 1}
+    du = d["dumped_outputs"]
+    assert du["view"] == (20 + 60 - 1) % d["config"]["views"] and du["dtype"] == "float32"
+    assert sorted(os.listdir(dump)) == sorted(f"{k}.npy" for k in du["arrays"]) and len(du["arrays"]) == 10
+
+
+def test_bench_breakdown_needs_full():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--breakdown"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 2 and "--full" in p.stderr, p.stderr[-2000:]
+
 
 def test_bench_dump_outputs_are_the_last_steps_own(tmp_path):
     """--dump-outputs writes what the LAST timed step computed: one view's images, radii and per-Gaussian gradients, float32, within 64 MB.
@@ -100,7 +133,7 @@ def test_bench_dump_outputs_are_the_last_steps_own(tmp_path):
     from animatablegaussians_amd.rasterizer import FusedRasterStep, GaussianRasterizationSettings
     dump, warmup, steps = tmp_path / "outputs", 20, 62
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
-                        "--no-full-step", "--no-stress", "--no-cpu-baseline", "--dump-outputs", str(dump)],
+                        "--full", "--no-full-step", "--no-stress", "--no-cpu-baseline", "--dump-outputs", str(dump)],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -156,7 +189,8 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("AG_DIST_BACKEND", None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "10"],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "10",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
