@@ -129,7 +129,10 @@ class DualStyleUNetOracle:
             x = fused_leaky_relu(x, self.p(f"style.{i + 1}.bias") * self.lr_mlp)
         return x
 
-    def forward(self, style, pose, view_feature1=None, view_feature2=None):
+    VIEW_STAGE = 4                                               # i == 8 at :881-883: after the stage's ToRGB, before the next comb conv
+
+    def encode(self, style, pose):
+        """The mapping network and the encoder -> (w_latent, levels, finest first)."""
         w_latent = self.latent(style)
         img = pose
         out = self.conv_layer(img, "conv_in", downsample=True)
@@ -140,24 +143,65 @@ class DualStyleUNetOracle:
             out = self.conv_layer(out, f"cond_convs.{n}.conv1")
             out = self.conv_layer(out, f"cond_convs.{n}.conv2", downsample=True)
             levels.append(out)
+        return w_latent, levels
+
+    @staticmethod
+    def add_view_feature(out, vf):
+        return out + F.interpolate(vf, out.shape[-2:], mode="bilinear")
+
+    def decode_stages(self, b, w_latent, levels, stages, out=None, skip=None, vf=None):
+        """Decoder stages ``stages`` of branch ``b`` from the state (out, skip) -> (out, skip); ``vf`` is added after stage VIEW_STAGE."""
         n_comb = self.n_enc + 1
+        for n in stages:
+            if n == 0:
+                out = self.conv_layer(levels[-1], f"comb_convs.{n_comb - 1}")
+            elif n < n_comb and self.comb_as_two_halves:
+                w = self.p(f"comb_convs.{n_comb - 1 - n}.0.weight")
+                c1, sc = out.shape[1], 1 / math.sqrt(w.shape[1] * 9)
+                y = F.conv2d(out, w[:, :c1] * sc, padding=1) + F.conv2d(levels[-1 - n], w[:, c1:] * sc, padding=1)
+                out = fused_leaky_relu(y, self.p(f"comb_convs.{n_comb - 1 - n}.1.bias"))
+            elif n < n_comb:
+                out = self.conv_layer(torch.cat([out, levels[-1 - n]], 1), f"comb_convs.{n_comb - 1 - n}")
+            out = self.styled_conv(out, f"convs{b}.{2 * n}", w_latent, self.p(f"noises.noise_{2 * n}"), True)
+            out = self.styled_conv(out, f"convs{b}.{2 * n + 1}", w_latent, self.p(f"noises.noise_{2 * n + 1}"), False)
+            skip = self.to_rgb(out, f"to_rgbs{b}.{n}", w_latent, skip)
+            if n == self.VIEW_STAGE and vf is not None:
+                out = self.add_view_feature(out, vf)
+        return out, skip
+
+    def forward(self, style, pose, view_feature1=None, view_feature2=None):
+        w_latent, levels = self.encode(style, pose)
         images = []
         for b, vf in ((1, view_feature1), (2, view_feature2)):
-            out = skip = None
-            for n in range(self.n_dec):
-                if n == 0:
-                    out = self.conv_layer(levels[-1], f"comb_convs.{n_comb - 1}")
-                elif n < n_comb and self.comb_as_two_halves:
-                    w = self.p(f"comb_convs.{n_comb - 1 - n}.0.weight")
-                    c1, sc = out.shape[1], 1 / math.sqrt(w.shape[1] * 9)
-                    y = F.conv2d(out, w[:, :c1] * sc, padding=1) + F.conv2d(levels[-1 - n], w[:, c1:] * sc, padding=1)
-                    out = fused_leaky_relu(y, self.p(f"comb_convs.{n_comb - 1 - n}.1.bias"))
-                elif n < n_comb:
-                    out = self.conv_layer(torch.cat([out, levels[-1 - n]], 1), f"comb_convs.{n_comb - 1 - n}")
-                out = self.styled_conv(out, f"convs{b}.{2 * n}", w_latent, self.p(f"noises.noise_{2 * n}"), True)
-                out = self.styled_conv(out, f"convs{b}.{2 * n + 1}", w_latent, self.p(f"noises.noise_{2 * n + 1}"), False)
-                skip = self.to_rgb(out, f"to_rgbs{b}.{n}", w_latent, skip)
-                if n == 4 and vf is not None:               # i == 8 at :881-883: after the stage's ToRGB, before the next comb conv
-                    out = out + F.interpolate(vf, out.shape[-2:], mode="bilinear")
+            _, skip = self.decode_stages(b, w_latent, levels, range(self.n_dec), vf=vf)
             images.append(haar_merge(skip))
         return torch.cat(images, 1)
+
+    def forward_views(self, style, pose, views, upstream=None, after_view=None):
+        """Several views of one pose, as the product's multi-view step evaluates them: the encoder and decoder stages 0..VIEW_STAGE once per
+        branch, then per view ``(vf1, vf2)`` of ``views`` the view feature added and the remaining stages -> the list of per-view images, each
+        what ``forward(style, pose, vf1, vf2)`` returns (the same operations on the same values).
+        ``upstream``: one gradient per view; each view's image is then back-propagated right after it is computed (the shared stages' graph is
+        kept for the next view, so their gradients accumulate the sum over the views, and one view's tail at a time is held in memory), the
+        images are returned detached and ``after_view(v)`` is called after view v's backward."""
+        w_latent, levels = self.encode(style, pose)
+        head = list(range(min(self.VIEW_STAGE + 1, self.n_dec)))
+        tail = list(range(self.VIEW_STAGE + 1, self.n_dec))
+        shared = {b: self.decode_stages(b, w_latent, levels, head) for b in (1, 2)}
+        images = []
+        for v, pair in enumerate(views):
+            parts = []
+            for b, vf in zip((1, 2), pair):
+                out, skip = shared[b]
+                if vf is not None:
+                    out = self.add_view_feature(out, vf)
+                _, skip = self.decode_stages(b, w_latent, levels, tail, out, skip)
+                parts.append(haar_merge(skip))
+            img = torch.cat(parts, 1)
+            if upstream is not None:
+                (img * upstream[v]).sum().backward(retain_graph=v + 1 < len(views))
+                img = img.detach()
+                if after_view is not None:
+                    after_view(v)
+            images.append(img)
+        return images

@@ -300,3 +300,199 @@ def cpu_threads():
     except (OSError, ValueError):
         pass
     return n
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The avatar's StyleUNets against the float64 CPU oracle (oracle/dual_styleunet_oracle.py): tests/test_styleunet_heads_gpu.py,
+# tests/test_multiview_tail_gpu.py
+# ---------------------------------------------------------------------------------------------------------------------------------
+SEEDS = {"position_net": 1101, "color_net": 2202, "other_net": 3303}
+NETS = ("position_net", "other_net", "color_net")            # the order get_maps returns the maps in
+
+
+class Math:
+    """``with Math(mode):`` the product's arithmetic mode (conv.set_math) for the block."""
+
+    def __init__(self, mode):
+        self.mode = mode
+
+    def __enter__(self):
+        from animatablegaussians_amd import conv as agc
+        self.prev = agc.set_math(self.mode)
+
+    def __exit__(self, *exc):
+        from animatablegaussians_amd import conv as agc
+        agc.set_math(self.prev)
+
+
+def rel(got, ref):
+    """max|got - ref| / max|ref| in float64 (``ref`` a CPU float64 tensor)."""
+    got = got.detach().double().cpu()
+    return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-300)
+
+
+def oracle_sd(sd, dt):
+    return {k: v.detach().to(dt).clone().requires_grad_(True) for k, v in sd.items()}
+
+
+def filled_avatar():
+    """AvatarNet.synthetic with view directions, the three networks filled with three synth.named_fill seeds (equal weights would hide a member
+    mix-up; the fill keeps non-zero biases and noise strengths), eval mode (colour style = the fixed buffer) -> (net, items, pose map [3, S, S])."""
+    import sys
+    import torch
+    from animatablegaussians_amd import synth
+    from animatablegaussians_amd.avatar import AvatarNet
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_avatar_net_gpu import _items
+    torch.manual_seed(31359)
+    net = AvatarNet.synthetic({'with_viewdirs': True})
+    for name, seed in SEEDS.items():
+        sub = getattr(net, name)
+        sub.load_reference_state_dict(synth.named_fill(sub.reference_state_dict(), seed=seed))
+    net.eval()
+    items = _items(net)
+    net.get_pose_map(items)
+    return net, items, items['smpl_pos_map'][:3].contiguous()
+
+
+def oracle_net(sd_gpu, style, pose, up, vfs, dt, learn):
+    """One network through the oracle on the CPU in ``dt`` -> (images float64, {key: gradient}, pose gradient, (vf1 grad, vf2 grad) or None)."""
+    import torch
+    from oracle.dual_styleunet_oracle import DualStyleUNetOracle
+    sd = {k: v.detach().cpu().to(dt).clone().requires_grad_(k in learn) for k, v in sd_gpu.items()}
+    p = pose.detach().cpu().to(dt).requires_grad_(True)
+    vs = [v.detach().cpu().to(dt).requires_grad_(True) for v in vfs] if vfs else None
+    img = DualStyleUNetOracle(sd).forward(style.detach().cpu().to(dt), p, *(vs or (None, None)))
+    (img * up.to(dt)).sum().backward()
+    grads = {k: sd[k].grad for k in learn}
+    return img.detach().double(), grads, p.grad.double(), ([v.grad.double() for v in vs] if vs else None)
+
+
+NBLK = 16
+
+
+def _sub(t, n=256):
+    f = t.detach().flatten()
+    step = max(1, f.numel() // n)
+    return f[::step][:n].double().cpu().clone()          # a copy: a float64 CPU gradient that keeps accumulating must not move the samples
+
+
+def summary(g):
+    """What the comparison reads of one gradient tensor: 256 samples, max |g|, and full-tensor statistics in float64 -- the sum, the sums of
+    16 contiguous blocks (dimension 0, output channels, slowest), their sums of magnitudes, the sum of squares."""
+    import torch
+    g = g.detach().double().flatten()
+    n = g.numel()
+    edges = [(n * b) // NBLK for b in range(NBLK + 1)]
+    blk = torch.stack([g[edges[b]:edges[b + 1]].sum() for b in range(NBLK)]).cpu()
+    blkabs = torch.stack([g[edges[b]:edges[b + 1]].abs().sum() for b in range(NBLK)]).cpu()
+    return {"sub": _sub(g), "max": float(g.abs().max()), "sum": float(g.sum()), "abs": float(g.abs().sum()), "blk": blk, "blkabs": blkabs,
+            "sq": float((g * g).sum()), "n": n}
+
+
+def deviation(s, ref):
+    """(sample deviation / max|ref|, block-sum, sum and square-sum deviations) of summary ``s`` from the float64 oracle's ``ref``."""
+    d = float((s["sub"] - ref["sub"]).abs().max()) / max(ref["max"], 1e-30)
+    d_sum = abs(s["sum"] - ref["sum"]) / max(ref["abs"], 1e-300)
+    d_blk = float(((s["blk"] - ref["blk"]).abs() / ref["blkabs"].clamp_min(1e-300)).max())
+    d_sq = abs(s["sq"] - ref["sq"]) / max(ref["sq"], 1e-300)
+    return d, d_sum, d_blk, d_sq
+
+
+# The end-to-end bars (test_styleunet_net.py::_golden_body with the live fp32 oracle as err32) on every parameter gradient of one network
+FULL_MULT = 5.0                        # full-tensor statistics: ours within 5x the fp32 oracle's at p50 / p90 / p99
+FULL_CAP = {"sum": 1e-2, "blk": 2e-2, "sq": 2e-2}
+FULL_CAP_SCALAR = 8e-2                 # one-element tensors (noise strengths): relative error of the number (sq: 2x)
+# One named exception to the caps, for the SEEDS above and the upstream gradients of test_styleunet_heads_gpu.py's `avatar` fixture (which
+# test_multiview_tail_gpu.py reuses for position_net).  position_net's convs1.11.activate.bias (64 numbers, so a "block" is 4 channels): block 11
+# deviates by 1.72e-2 of its magnitude in the fp32 oracle, the fp32 oracle with the comb convolutions re-associated AND the product in split_f16
+# -- identical to four digits in three different arithmetics -- 0.93e-2 in the product's fp32 mode, 2.44e-2 in split_bf16 (one network).  The
+# channel sums are ill-conditioned (sum|terms| / |sum| up to 1.4e4 in float64); the product's own reduction matches a float64 sum of its own
+# pre-activation gradient to 1e-9 of sum|terms|; the deviation is leaky-ReLU slope selections at pre-activations within fp32 rounding of zero,
+# each moving the block by a fixed amount: a handful of pixels, not arithmetic error.  Cap for this one statistic: 2x the fp32 oracle's 1.72e-2.
+FULL_CAP_NAMED = {("position_net", "convs1.11.activate.bias", "blk"): 3.5e-2}
+
+
+def check_network_grads(tag, name, grads, learn, s64, e32, named=None):
+    """Every parameter gradient ``grads[k]`` (k in ``learn``) of network ``name`` against the float64 oracle's summaries ``s64`` with the fp32
+    oracle's deviations ``e32`` as the yardstick: sample deviations at p50..p95 within 3x the oracle's, p99 (noise strengths aside) within 3x,
+    per-tensor caps; full-tensor statistics (sum, block sums, square sum) within 5x the oracle's at p50 / p90 / p99 and per-tensor caps.
+    ``named``: {parameter key: cap} -- a caller's named exceptions, with their measured evidence written where they are given: the cap replaces
+    the per-tensor caps of that tensor (its samples and full-tensor statistics; the square sum 2x).
+    Prints the statistics; returns the worst ratio of a measured value to its bar."""
+    named = named or {}
+    rows, full = [], []
+    for k in learn:
+        gk = grads[k]
+        assert gk is not None, (name, k)
+        d, d_sum, d_blk, d_sq = deviation(summary(gk), s64[k])
+        r, r_sum, r_blk, r_sq = e32[k]
+        rows.append((d, r, k))
+        full.append((k, d_sum, r_sum, d_blk, r_blk, d_sq, r_sq, s64[k]["n"]))
+    worst = 0.0
+    ours, ref = np.array([o for o, _, _ in rows]), np.array([r for _, r, _ in rows])
+    print(f"[e2e] {tag} {name}: gradient rows over {len(rows)} tensors, ours / oracle fp32: "
+          + " ".join(f"p{q} {np.percentile(ours, q):.2e}/{np.percentile(ref, q):.2e}" for q in (50, 75, 90, 95, 99, 100)))
+    for q in (50, 75, 90, 95):
+        worst = max(worst, np.percentile(ours, q) / max(3 * np.percentile(ref, q), 1e-300))
+        assert np.percentile(ours, q) <= 3 * np.percentile(ref, q), (name, q, np.percentile(ours, q), np.percentile(ref, q))
+    tens = [(o, r) for o, r, k in rows if not k.endswith("noise.weight")]
+    o99, r99 = np.percentile([o for o, _ in tens], 99), np.percentile([r for _, r in tens], 99)
+    worst = max(worst, o99 / max(3 * r99, 1e-300))
+    assert o99 <= 3 * r99, (name, o99, r99)
+    # per-tensor caps of _golden_body: 1e-2, and 5e-2 for the noise strengths -- except a noise strength on which the fp32 oracle ITSELF
+    # misses 5e-2 (a one-number gradient, a sum over a whole map with cancellation): 2x the oracle's own deviation there.  Measured: other_net
+    # convs2.11.noise.weight, oracle fp32 0.142 of the value, ours 0.128-0.149 in the three modes on both paths; no other tensor
+    for o, r, k in rows:
+        cap = 1e-2
+        if k.endswith("noise.weight"):
+            cap = 2 * r if r > 5e-2 else 5e-2
+        cap = named.get(k, cap)
+        worst = max(worst, o / cap)
+        assert o <= cap, (name, k, o, r)
+    fo = {kk: np.array([r[i] for r in full]) for kk, i in (("sum", 1), ("rsum", 2), ("blk", 3), ("rblk", 4), ("sq", 5), ("rsq", 6))}
+    print(f"[e2e] {tag} {name}: full-tensor statistics, ours/oracle fp32 at p50 p90 p99 max: "
+          + "; ".join(f"{kk}: " + " ".join(f"{np.percentile(fo[kk], q):.1e}/{np.percentile(fo['r' + kk], q):.1e}" for q in (50, 90, 99, 100))
+                      for kk in ("sum", "blk", "sq"))
+          + " | p99 ratio " + " ".join(f"{kk} {np.percentile(fo[kk], 99) / max(np.percentile(fo['r' + kk], 99), 1e-7):.2f}" for kk in ("sum", "blk", "sq")))
+    for kk in ("sum", "blk", "sq"):
+        for q in (50, 90, 99):
+            lim = FULL_MULT * max(np.percentile(fo["r" + kk], q), 1e-7)
+            worst = max(worst, np.percentile(fo[kk], q) / lim)
+            assert np.percentile(fo[kk], q) <= lim, (name, kk, q, np.percentile(fo[kk], q), np.percentile(fo["r" + kk], q))
+        col = {"sum": 1, "blk": 3, "sq": 5}[kk]
+        for r in full:
+            cap = (2 * FULL_CAP_SCALAR if kk == "sq" else FULL_CAP_SCALAR) if r[7] == 1 else FULL_CAP[kk]
+            cap = FULL_CAP_NAMED.get((name, r[0], kk), cap)
+            if r[7] == 1 and r[0].endswith("noise.weight") and r[col + 1] > cap:
+                cap = 2 * r[col + 1]          # the noise-strength rule of the rows above: the fp32 oracle itself misses the cap (convs2.11, 0.142)
+            if r[0] in named:
+                cap = named[r[0]] * (2 if kk == "sq" else 1)
+            worst = max(worst, r[col] / cap)
+            assert r[col] <= cap, (name, kk, r)
+    return worst
+
+
+def check_maps(maps, ref_maps, err32, tag):
+    """Forward maps against the float64 oracle: max|ours - o64| / max|o64| <= 1e-4 each.  Returns the worst ratio to the bar."""
+    worst = 0.0
+    for name, m in maps:
+        ref = ref_maps[name]
+        assert tuple(m.shape) == tuple(ref.shape), (name, tuple(m.shape))
+        d = rel(m, ref)
+        print(f"[e2e] {tag} forward {name}: ours {d:.2e} oracle-fp32 {err32[name]:.2e} (bar 1e-4)")
+        worst = max(worst, d / 1e-4)
+        assert d <= 1e-4, (tag, name, d)
+    return worst
+
+
+def check_vf_grad(got, ref, what):
+    """An ACTIVATION gradient (2 M elements): leaky-ReLU slope flips near zero make isolated elements differ by factors, so relative L2 and the
+    fraction of elements off by more than 1e-3 of the largest (the bars of test_grouped_gpu.py::test_three_networks_as_one_chain...).
+    Returns the worst ratio to the bars."""
+    got = got.detach().double().cpu()
+    l2 = float((got - ref).norm() / ref.norm())
+    off = float(((got - ref).abs() > 1e-3 * float(ref.abs().max())).double().mean())
+    print(f"[e2e] {what}: relative L2 {l2:.2e} (bar 3e-3), fraction off by > 1e-3 of max {off:.2e} (bar 5e-3)")
+    assert l2 <= 3e-3 and off <= 5e-3, (what, l2, off)
+    return max(l2 / 3e-3, off / 5e-3)

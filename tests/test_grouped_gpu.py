@@ -406,3 +406,61 @@ def test_multi_view_gradients_are_the_sum_over_the_views(net):
         worst = max(worst, err)
         assert err <= (2e-2 if k.endswith("noise.weight") else 5e-3), (k, err)
     print(f"three views at once vs three single-view passes: worst relative parameter-gradient deviation {worst:.2e} over {len(probe)} probes")
+
+
+def test_sixteen_view_training_step_equals_sixteen_single_view_renders(net):
+    """The 16-view training step (bench_avatar.py --views 16: render_views of 16 cameras of one pose, the colour network's view-dependent tail in
+    three grouped chunks of at most 16 members) against render() of each camera, in eval mode: every view's maps and image under the bars of
+    test_grouped_multi_view_equals_per_view_renders; after a backward of the sum of the views' losses.training_loss, EVERY parameter gradient of
+    the three networks against the sum of the 16 single-view passes' gradients, under the summation-order bar of
+    test_multi_view_gradients_are_the_sum_over_the_views."""
+    import torch
+    from animatablegaussians_amd import losses, synth
+    base = _items(net)
+    net.get_pose_map(base)
+    cams = synth.free_view_cameras(16, img=1024)
+    views = [{'extr': torch.from_numpy(np.ascontiguousarray(c["extr"])).float().cuda(),
+              'intr': torch.from_numpy(np.ascontiguousarray(c["intr"])).float().cuda(), 'img_w': 1024, 'img_h': 1024} for c in cams]
+    pose_items = {k: base[k] for k in ('smpl_pos_map', 'cano2live_jnt_mats', 'cano2live_jnt_mats_woRoot')}
+    net.eval()
+    mask = synth.body_mask(1024)
+    m = torch.from_numpy(mask.copy()).cuda()
+    gt = {'color_img': torch.rand(1024, 1024, 3, generator=torch.Generator().manual_seed(17)).cuda(), 'mask_img': m,
+          'boundary_mask_img': torch.zeros_like(m), 'mask_bbox': losses.mask_bbox(mask)}
+    bg = torch.zeros(3, device="cuda")
+    weights = {'l1': 1.0, 'mask': 0.1, 'offset': 0.005}
+    params = {(n, k): getattr(net, n)._p(k) for n in ("position_net", "other_net", "color_net") for k in getattr(net, n)._learnable}
+    keys = ('pos_map', 'cano_tex_map', 'offset', 'rgb_map')
+
+    net.zero_grad(set_to_none=True)
+    multi = net.render_views(pose_items, views, bg_color=(0., 0., 0.))
+    assert len(multi) == 16
+    sum(losses.training_loss(r, gt, bg, weights)[0] for r in multi).backward()
+    torch.cuda.synchronize()
+    got = {key: (p.grad.clone() if p.grad is not None else None) for key, p in params.items()}
+    outs = [{k: r[k].detach().clone() for k in keys} for r in multi]
+    del multi
+    net.zero_grad(set_to_none=True)
+    for v, view in enumerate(views):
+        single = net.render({**pose_items, **view}, bg_color=(0., 0., 0.))
+        for key in ('pos_map', 'cano_tex_map', 'offset'):
+            _close(outs[v][key], single[key], f"view {v} {key}", tol=2e-5)
+        # the image goes through the rasterizer's discrete decisions: compare away from them
+        d = (outs[v]['rgb_map'] - single['rgb_map'].detach()).abs()
+        assert float((d > 1e-3).float().mean()) < 1e-3, (v, float((d > 1e-3).float().mean()))
+        losses.training_loss(single, gt, bg, weights)[0].backward()
+        del single
+    torch.cuda.synchronize()
+    worst, n = 0.0, 0
+    for key, p in params.items():
+        want = p.grad
+        assert (want is None) == (got[key] is None), key
+        if want is None:
+            continue
+        scale = float(want.abs().max())
+        assert scale > 0, key
+        err = float((got[key] - want).abs().max()) / scale
+        worst, n = max(worst, err), n + 1
+        assert err <= (2e-2 if key[1].endswith("noise.weight") else 5e-3), (key, err)
+    net.zero_grad(set_to_none=True)
+    print(f"16 views at once vs 16 single-view renders: worst relative parameter-gradient deviation {worst:.2e} over {n} tensors")

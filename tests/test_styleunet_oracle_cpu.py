@@ -86,3 +86,60 @@ def test_the_one_number_gradients_move_by_factors_when_the_reference_arithmetic_
     v1, v2 = np.array([one[k] for k in tens]), np.array([two[k] for k in tens])
     for q in (50, 90):                                                     # ... the bulk of the tensors does not
         assert 0.6 <= np.percentile(v2, q) / np.percentile(v1, q) <= 1.6, (q, np.percentile(v1, q), np.percentile(v2, q))
+
+
+def test_forward_views_is_forward_per_view_and_sums_the_shared_gradients():
+    """DualStyleUNetOracle.forward_views -- the encoder and decoder stages 0..4 once per branch, the view feature and the tail per view, the yardstick
+    of tests/test_multiview_tail_gpu.py -- against ``forward`` run once per view, in float64, on a network small enough for the CPU (256 -> 512,
+    middle 4: the same stage layout, the view stage followed by a comb convolution).  Every view's image must equal forward's BIT FOR BIT (the same
+    operations on the same values); after a backward of per-view upstream gradients every parameter gradient and every view feature's gradient must
+    equal the sum of the single-view passes' up to float64 summation order."""
+    from animatablegaussians_amd import synth
+    from animatablegaussians_amd.styleunet import DualStyleUNet
+    from oracle.dual_styleunet_oracle import DualStyleUNetOracle
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    net = DualStyleUNet(inp_size=256, out_size=512, middle_size=4, channel_multiplier=1, style_dim=64)
+    base = {k: v.double() for k, v in synth.named_fill(net.reference_state_dict(), seed=77).items()}
+    learn = [k for k in base if not k.startswith("noises.")]
+
+    def make():
+        sd = {k: v.clone().requires_grad_(k in learn) for k, v in base.items()}
+        return sd, DualStyleUNetOracle(sd, inp_size=256, out_size=512, middle_size=4)
+    g = torch.Generator().manual_seed(78)
+    style = torch.randn(1, 64, generator=g, dtype=torch.float64)
+    pose = torch.randn(1, 3, 256, 256, generator=g, dtype=torch.float64)
+    vfs = [[torch.randn(1, 128, 32, 32, generator=g, dtype=torch.float64) for _ in range(2)] for _ in range(2)]
+    ups = [torch.randn(1, 6, 512, 512, generator=g, dtype=torch.float64) for _ in range(2)]
+    _, o = make()
+    assert o.VIEW_STAGE + 1 < o.n_enc + 1 and o.VIEW_STAGE + 1 < o.n_dec            # the tail starts with a comb convolution, as in the product
+
+    # forward only: bit for bit
+    with torch.no_grad():
+        multi = o.forward_views(style, pose, vfs)
+        for v in range(2):
+            assert torch.equal(multi[v], o.forward(style, pose, *vfs[v])), v
+        # a view without features, and features on one branch only
+        mixed = o.forward_views(style, pose, [(None, None), (vfs[1][0], None)])
+        assert torch.equal(mixed[0], o.forward(style, pose)) and torch.equal(mixed[1], o.forward(style, pose, vfs[1][0], None))
+
+    # with the upstream gradients: one backward per view, the shared gradients summed
+    sd_m, o_m = make()
+    vm = [[t.clone().requires_grad_(True) for t in pair] for pair in vfs]
+    seen = []
+    imgs = o_m.forward_views(style, pose, vm, upstream=ups, after_view=lambda v: seen.append((v, sd_m["convs1.0.conv.weight"].grad.clone())))
+    assert [v for v, _ in seen] == [0, 1] and all(not i.requires_grad for i in imgs)
+    sd_s, o_s = make()
+    vs = [[t.clone().requires_grad_(True) for t in pair] for pair in vfs]
+    for v in range(2):
+        img = o_s.forward(style, pose, *vs[v])
+        assert torch.equal(img.detach(), imgs[v]), v
+        (img * ups[v]).sum().backward()
+        if v == 0:                                                                    # after view 0: the first view's gradient alone
+            assert torch.allclose(seen[0][1], sd_s["convs1.0.conv.weight"].grad, rtol=0, atol=1e-12 * float(seen[0][1].abs().max()))
+    for k in learn:
+        a, b = sd_m[k].grad, sd_s[k].grad
+        assert a is not None and b is not None, k
+        assert float((a - b).abs().max()) <= 1e-10 * max(float(b.abs().max()), 1e-300), (k, float((a - b).abs().max()), float(b.abs().max()))
+    for v in range(2):
+        for b in range(2):
+            assert torch.equal(vm[v][b].grad, vs[v][b].grad) or float((vm[v][b].grad - vs[v][b].grad).abs().max()) <= 1e-12 * float(vs[v][b].grad.abs().max())
