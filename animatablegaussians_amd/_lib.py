@@ -221,6 +221,14 @@ SYMBOLS = [
     ("ag_mat4_mul_inverse_backward", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     ("ag_smplx_backward", ctypes.c_int, [ctypes.POINTER(AgSmplxModel), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("ag_smplx_keypoints", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    ("ag_smplx_saved_floats", c_sz, [ctypes.POINTER(AgSmplxModel), c_i32]),
+    ("ag_smplx_forward_keep", ctypes.c_int, [ctypes.POINTER(AgSmplxModel), c_i32] + [c_vp] * 7 + [c_sz, c_vp, c_sz, c_vp]),
+    ("ag_smplx_keypoints_backward", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    ("ag_smplx_vertex_backward_workspace_floats", c_sz, [ctypes.POINTER(AgSmplxModel), c_i32]),
+    ("ag_smplx_vertex_backward", ctypes.c_int, [ctypes.POINTER(AgSmplxModel), c_i32] + [c_vp] * 7 + [c_sz, c_vp]),
+    ("ag_smplx_shape_backward_workspace_floats", c_sz, [ctypes.POINTER(AgSmplxModel), c_i32]),
+    ("ag_smplx_shape_backward", ctypes.c_int, [ctypes.POINTER(AgSmplxModel), c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    ("ag_smplx_backward_full", ctypes.c_int, [ctypes.POINTER(AgSmplxModel), c_i32] + [c_vp] * 12),
     # include/ag_avatar.h
     ("ag_gather_activate_forward", ctypes.c_int, [ctypes.POINTER(AgGatherArgs), c_vp]),
     ("ag_gather_activate_backward", ctypes.c_int, [ctypes.POINTER(AgGatherArgs), c_vp, c_vp, c_vp, c_vp]),

@@ -10,6 +10,8 @@
 //                  10475-long reduction per joint and pose)
 //   skin_kernel    pose_offsets = features . posedirs (the 61 MB stream), v_posed, T = W . A, vertices
 //                  workgroup = 32 vertices x 8 slices of the 486 features; lanes along coordinates (256-B segments)
+// The backward of the kinematic chain is one launch (chain_backward_kernel); the backward of the vertex path (key points, skinning,
+// the two bases transposed) is the block of kernels after it, ahead of the host functions.
 #include "ag_common.h"
 #include "../../include/ag_smplx.h"
 
@@ -165,7 +167,8 @@ __global__ void __launch_bounds__(kSkinThreads) smplx_skin_kernel(float* __restr
                                                                  const float* __restrict__ pose_feature,
                                                                  const float* __restrict__ v_shaped, const float* __restrict__ A,
                                                                  const float* __restrict__ lbs_weights,
-                                                                 const float* __restrict__ transl, int V, int J, int P)
+                                                                 const float* __restrict__ transl, float* __restrict__ v_posed_out,
+                                                                 int V, int J, int P)
 {
     extern __shared__ float smem[];
     float* s_feat = smem;                                   // [NBATCH][P]
@@ -210,7 +213,9 @@ __global__ void __launch_bounds__(kSkinThreads) smplx_skin_kernel(float* __restr
     if (worker && live) {
         float off = 0.f;
         for (int s = 0; s < kSkinSlices; ++s) off += s_part[(s * NBATCH + wb) * kSkinCoords + cx];
-        s_vp[wb * kSkinCoords + cx] = off + v_shaped[(size_t)wb * n_coord + coord];     // lbs.py:233
+        const float vp = off + v_shaped[(size_t)wb * n_coord + coord];                  // lbs.py:233
+        s_vp[wb * kSkinCoords + cx] = vp;
+        if (v_posed_out) v_posed_out[(size_t)wb * n_coord + coord] = vp;                // kept for ag_smplx_vertex_backward
     }
     __syncthreads();
     if (worker && live) {
@@ -317,12 +322,17 @@ __device__ __forceinline__ void rodrigues_backward(const float* rv, const float*
 // the tree levels from the deepest to the root.  A parent gathers its children's contributions in ascending joint order, so the
 // result does not depend on scheduling.  Inputs dA [B][J][4][4] (row 3 unused) and djoints [B][J][3], either may be NULL.
 // Outputs: dpose [B][J][3]; dtransl [B][3] (NULL: skipped); dcomps [B][NB] through the folded joint_dirs (NULL: skipped).
+// EXT (ag_smplx_backward_full) adds what the vertex path hands over, each NULL or present: dAs [B][J][12] on the un-translated matrices
+// the skinning read (joins dA everywhere except in dtransl), dfeat [B][J-1][9] on the local rotations R[1:] (joins dR ahead of the
+// Rodrigues backward), dtr_add [B][3] and dcomps_add [B][NB] (added to the two outputs last).  EXT = false is the kernel as it was.
+template <bool EXT>
 __global__ void __launch_bounds__(64) smplx_chain_backward_kernel(float* __restrict__ dpose, float* __restrict__ dtransl,
                                                                  float* __restrict__ dcomps, const float* __restrict__ dA,
                                                                  const float* __restrict__ djoints, const float* __restrict__ full_pose,
                                                                  const float* __restrict__ comps, const float* __restrict__ joint_template,
                                                                  const float* __restrict__ joint_dirs, const int* __restrict__ parents,
-                                                                 int J, int NB)
+                                                                 int J, int NB, const float* __restrict__ dAs, const float* __restrict__ dfeat,
+                                                                 const float* __restrict__ dtr_add, const float* __restrict__ dcomps_add)
 {
     __shared__ Affine s_glob[kMaxJoints];
     __shared__ float s_rest[kMaxJoints][3];
@@ -382,20 +392,27 @@ __global__ void __launch_bounds__(64) smplx_chain_backward_kernel(float* __restr
         const float* a = dA ? dA + ((size_t)b * J + j) * 16 : nullptr;
         const float* dj = djoints ? djoints + ((size_t)b * J + j) * 3 : nullptr;
         const Affine& g = s_glob[j];
+        const float* as = EXT && dAs ? dAs + ((size_t)b * J + j) * 12 : nullptr;
+        float dtr[3];     // the part of dGt that transl sees: dAs belongs to the matrices before transl was added
         for (int r = 0; r < 3; ++r) {
-            const float dcol = a ? a[4 * r + 3] : 0.f;
+            float dcol = a ? a[4 * r + 3] : 0.f;
+            dtr[r] = dcol + (dj ? dj[r] : 0.f);
+            if (EXT && as) dcol += as[4 * r + 3];
             dGt[r] = dcol + (dj ? dj[r] : 0.f);
             for (int c = 0; c < 3; ++c) {
-                dGr[3 * r + c] = (a ? a[4 * r + c] : 0.f) - dcol * rest[c];
+                float da = a ? a[4 * r + c] : 0.f;
+                if (EXT && as) da += as[4 * r + c];
+                dGr[3 * r + c] = da - dcol * rest[c];
                 drest[c] -= g.r[3 * r + c] * dcol;
             }
         }
-        for (int r = 0; r < 3; ++r) s_ct[j][r] = dGt[r];
+        for (int r = 0; r < 3; ++r) s_ct[j][r] = EXT ? dtr[r] : dGt[r];      // read by the dtransl sum only; the level loop rewrites it
     }
     __syncthreads();
     if (dtransl && j < 3) {           // body_models.py:1272-1275: transl is added to every A_j[:3, 3] and every joint
         float acc = 0.f;
         for (int k = 0; k < J; ++k) acc += s_ct[k][j];
+        if (EXT && dtr_add) acc += dtr_add[3 * b + j];
         dtransl[3 * b + j] = acc;
     }
     __syncthreads();
@@ -423,6 +440,8 @@ __global__ void __launch_bounds__(64) smplx_chain_backward_kernel(float* __restr
                 for (int k = 0; k < 3; ++k) dt[k] = dGt[k];
             }
             for (int k = 0; k < 3; ++k) s_dt[j][k] = dt[k];
+            if (EXT && dfeat && j >= 1)       // lbs.py:221: pose_feature = R[1:] - I
+                for (int k = 0; k < 9; ++k) dR[k] += dfeat[(size_t)b * 9 * (J - 1) + 9 * (j - 1) + k];
             rodrigues_backward(full_pose + ((size_t)b * J + j) * 3, dR, dpose + ((size_t)b * J + j) * 3);
         }
         __syncthreads();
@@ -450,6 +469,7 @@ __global__ void __launch_bounds__(64) smplx_chain_backward_kernel(float* __restr
             float acc = 0.f;
             for (int k = 0; k < J; ++k)
                 for (int c = 0; c < 3; ++c) acc = fmaf(s_drest[k][c], joint_dirs[(size_t)(3 * k + c) * NB + l], acc);
+            if (EXT && dcomps_add) acc += dcomps_add[(size_t)b * NB + l];
             dcomps[(size_t)b * NB + l] = acc;
         }
 }
@@ -527,6 +547,216 @@ __global__ void __launch_bounds__(64) mat4_mul_inverse_backward_kernel(float* __
         }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Backward of the vertex path (ag_smplx_vertex_backward, ag_smplx_keypoints_backward, ag_smplx_shape_backward).  No float atomics:
+// every sum has a fixed order, so two calls give the same bits.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int kVbVerts = 64;        // vertices per workgroup of skin_backward_kernel = one slab of the joint sums
+constexpr int kVbThreads = 768;     // >= 12 J + 3 for J = 55: one pass over the slab row
+constexpr int kPdThreads = 1024;    // posedirs_t_kernel: one workgroup per basis row
+constexpr int kSdCoords = 256;      // dirs_t_kernel: coordinates per workgroup = one slab of the component sums
+
+// Key points -> vertices: dverts[b][idx[k][t]] += w[k][t] dkp[b][k].  Vertex ids repeat (landmark triangles share vertices, the vertex
+// picks carry theirs three times), so the FIRST entry that names a vertex owns it: it adds its own and every later entry's term in
+// ascending entry order and stores once.  dverts must hold zeros (or a gradient to add to) before the launch.  One workgroup per pose;
+// the 3 K ids and weights sit in LDS for the scans.
+__global__ void __launch_bounds__(256) smplx_keypoints_backward_kernel(float* __restrict__ dverts, const float* __restrict__ dkp,
+                                                                      const int* __restrict__ idx, const float* __restrict__ w, int V, int K)
+{
+    extern __shared__ float smem[];
+    const int n = 3 * K;
+    int* s_idx = reinterpret_cast<int*>(smem);       // [3 K]
+    float* s_w = smem + n;                            // [3 K]
+    float* s_g = s_w + n;                             // [3 K]: dkp of this pose
+    const int b = blockIdx.x;
+    for (int e = threadIdx.x; e < n; e += 256) {
+        s_idx[e] = idx[e];
+        s_w[e] = w[e];
+        s_g[e] = dkp[(size_t)b * n + e];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < n; e += 256) {
+        const int v = s_idx[e];
+        if (v < 0 || v >= V) continue;
+        bool owner = true;
+#pragma unroll 8
+        for (int q = 0; q < e; ++q) owner = owner && s_idx[q] != v;
+        if (!owner) continue;
+        float* dst = dverts + ((size_t)b * V + v) * 3;
+        float a0 = dst[0], a1 = dst[1], a2 = dst[2];
+#pragma unroll 8
+        for (int q = e; q < n; ++q)
+            if (s_idx[q] == v) {
+                const float wq = s_w[q];
+                const float* gk = s_g + 3 * (q / 3);
+                a0 = fmaf(wq, gk[0], a0);
+                a1 = fmaf(wq, gk[1], a1);
+                a2 = fmaf(wq, gk[2], a2);
+            }
+        dst[0] = a0; dst[1] = a1; dst[2] = a2;
+    }
+}
+
+// Skinning backward for 64 vertices of one pose.  g = dL/dvertices.
+//   dvp[v] = T_v[:3,:3]^T g[v],  T_v = sum_j W[v][j] A_skin[j]                                (lbs.py:241-246)
+//   slab[wg][b][j][r][c] = sum_{v in the workgroup, ascending} W[v][j] g[v][r] [v_posed[v]; 1][c]     -> dL/dA_skin after the slab sum
+//   slab[wg][b][12 J + r] = sum_v g[v][r]                                                             -> dL/dtransl
+__global__ void __launch_bounds__(kVbThreads) smplx_skin_backward_kernel(float* __restrict__ dvp, float* __restrict__ slabs,
+                                                                        const float* __restrict__ g, const float* __restrict__ v_posed,
+                                                                        const float* __restrict__ A_skin,
+                                                                        const float* __restrict__ lbs_weights, int V, int J)
+{
+    extern __shared__ float smem[];
+    float* s_W = smem;                          // [kVbVerts][J]
+    float* s_A = s_W + kVbVerts * J;            // [J][12]
+    float* s_g = s_A + J * 12;                  // [kVbVerts][4]  (g, 0)
+    float* s_x = s_g + kVbVerts * 4;            // [kVbVerts][4]  (v_posed, 1)
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int v0 = blockIdx.x * kVbVerts;
+    const int nv = V - v0 < kVbVerts ? V - v0 : kVbVerts;
+    const int width = 12 * J + 3;
+    for (int i = tid; i < kVbVerts * J; i += kVbThreads) s_W[i] = i < nv * J ? lbs_weights[(size_t)v0 * J + i] : 0.f;
+    for (int i = tid; i < J * 12; i += kVbThreads) s_A[i] = A_skin[(size_t)b * J * 12 + i];
+    if (tid < 4 * kVbVerts) {
+        const int lv = tid >> 2, c = tid & 3;
+        const bool in = lv < nv && c < 3;
+        const size_t at = ((size_t)b * V + v0 + lv) * 3 + c;
+        s_g[tid] = in ? g[at] : 0.f;
+        s_x[tid] = in ? v_posed[at] : (c == 3 && lv < nv ? 1.f : 0.f);
+    }
+    __syncthreads();
+    if (tid < 3 * kVbVerts) {
+        const int lv = tid / 3, c = tid % 3;
+        if (lv < nv) {
+            const float g0 = s_g[4 * lv], g1 = s_g[4 * lv + 1], g2 = s_g[4 * lv + 2];
+            const float* wv = s_W + lv * J;
+            float acc = 0.f;
+            for (int j = 0; j < J; ++j) {
+                const float* Aj = s_A + 12 * j + c;
+                acc = fmaf(wv[j], fmaf(Aj[8], g2, fmaf(Aj[4], g1, Aj[0] * g0)), acc);
+            }
+            dvp[((size_t)b * V + v0 + lv) * 3 + c] = acc;
+        }
+    }
+    float* slab = slabs + ((size_t)blockIdx.x * gridDim.y + b) * width;
+    for (int e = tid; e < width; e += kVbThreads) {
+        float acc = 0.f;
+        if (e < 12 * J) {
+            const int j = e / 12, r = (e % 12) >> 2, c = e & 3;
+            for (int lv = 0; lv < kVbVerts; ++lv) acc = fmaf(s_W[lv * J + j] * s_g[4 * lv + r], s_x[4 * lv + c], acc);
+        } else {
+            const int r = e - 12 * J;
+            for (int lv = 0; lv < kVbVerts; ++lv) acc += s_g[4 * lv + r];
+        }
+        slab[e] = acc;
+    }
+}
+
+// Sum over slabs of one column i of slabs [n_slab][total], by a workgroup of 16 columns x 16 slab groups (tid = 16 q + column): group q
+// adds slabs q, q + 16, q + 32, ... in ascending order, then the 16 groups are added in ascending q.  Returns the sum in the threads
+// with q = 0 (tid < 16).  Every thread of the workgroup must call it.
+__device__ __forceinline__ float slab_column_sum(const float* __restrict__ slabs, int n_slab, int total, int i, float* s_red)
+{
+    const int q = threadIdx.x >> 4;
+    float acc = 0.f;
+    if (i < total) {
+#pragma unroll 4
+        for (int sl = q; sl < n_slab; sl += 16) acc += slabs[(size_t)sl * total + i];
+    }
+    s_red[threadIdx.x] = acc;
+    __syncthreads();
+    float r = 0.f;
+    if (threadIdx.x < 16)
+        for (int k = 0; k < 16; ++k) r += s_red[16 * k + threadIdx.x];
+    return r;
+}
+
+// The slab sums of the vertex backward in one launch.  Workgroups [0, n_skin_blocks): dL/dA_skin [B][J][12] and dL/dtransl [B][3] from
+// the slabs [n_skin_slab][B][12 J + 3] of smplx_skin_backward_kernel; the rest: out [dirs_total] from the slabs
+// [n_dirs_slab][dirs_total] of smplx_dirs_t_kernel.  Order: slab_column_sum.
+__global__ void __launch_bounds__(256) smplx_slab_sums_kernel(float* __restrict__ dAs, float* __restrict__ dtr,
+                                                             const float* __restrict__ skin_slabs, int n_skin_slab, int B, int J,
+                                                             int n_skin_blocks, float* __restrict__ dcomps,
+                                                             const float* __restrict__ dirs_slabs, int n_dirs_slab, int dirs_total)
+{
+    __shared__ float s_red[256];
+    const int li = threadIdx.x & 15;
+    if ((int)blockIdx.x < n_skin_blocks) {
+        const int width = 12 * J + 3, total = B * width;
+        const int i = blockIdx.x * 16 + li;
+        const float r = slab_column_sum(skin_slabs, n_skin_slab, total, i, s_red);
+        if (threadIdx.x < 16 && i < total) {
+            const int b = i / width, e = i % width;
+            if (e < 12 * J) dAs[(size_t)b * 12 * J + e] = r;
+            else dtr[3 * b + (e - 12 * J)] = r;
+        }
+    } else {
+        const int i = (blockIdx.x - n_skin_blocks) * 16 + li;
+        const float r = slab_column_sum(dirs_slabs, n_dirs_slab, dirs_total, i, s_red);
+        if (threadIdx.x < 16 && i < dirs_total) dcomps[i] = r;
+    }
+}
+
+// The pose-corrective basis, transposed: dfeat[b][p] = sum_c posedirs[p][c] dvp[b][c].  One workgroup per row p (125.7 KB, contiguous),
+// the row read ONCE for the NBATCH poses; dvp (126 KB per pose) comes from cache.  A thread walks c = tid, tid + 1024, ... in ascending
+// order, eight loads in flight; then lanes by xor-shuffle (32, 16, ... 1), then the 16 waves in ascending order.
+template <int NBATCH>
+__global__ void __launch_bounds__(kPdThreads) smplx_posedirs_t_kernel(float* __restrict__ dfeat, const float* __restrict__ posedirs,
+                                                                     const float* __restrict__ dvp, int n_coord, int P)
+{
+    __shared__ float s_part[NBATCH][kPdThreads / 64];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const float* row = posedirs + (size_t)p * n_coord;
+    float acc[NBATCH];
+    for (int b = 0; b < NBATCH; ++b) acc[b] = 0.f;
+    int c = tid;
+    for (; c + 7 * kPdThreads < n_coord; c += 8 * kPdThreads) {
+        float d[8];
+        for (int u = 0; u < 8; ++u) d[u] = row[c + u * kPdThreads];
+        for (int b = 0; b < NBATCH; ++b) {
+            const float* x = dvp + (size_t)b * n_coord + c;
+            for (int u = 0; u < 8; ++u) acc[b] = fmaf(d[u], x[u * kPdThreads], acc[b]);
+        }
+    }
+#pragma unroll 4
+    for (; c < n_coord; c += kPdThreads) {
+        const float d = row[c];
+        for (int b = 0; b < NBATCH; ++b) acc[b] = fmaf(d, dvp[(size_t)b * n_coord + c], acc[b]);
+    }
+    for (int b = 0; b < NBATCH; ++b) {
+        float a = acc[b];
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if ((tid & 63) == 0) s_part[b][tid >> 6] = a;
+    }
+    __syncthreads();
+    if (tid < NBATCH) {
+        float a = 0.f;
+        for (int wv = 0; wv < kPdThreads / 64; ++wv) a += s_part[tid][wv];
+        dfeat[(size_t)tid * P + p] = a;
+    }
+}
+
+// The shape basis, transposed, for 256 coordinates of one pose: slab[wg][b][k] = sum_{c in the workgroup} dirs[c][k] x[b][c]
+// (lanes by xor-shuffle, then the four waves in ascending order).  x = dL/dv_posed or dL/dv_shaped.
+__global__ void __launch_bounds__(kSdCoords) smplx_dirs_t_kernel(float* __restrict__ slabs, const float* __restrict__ dirs,
+                                                                const float* __restrict__ x, int n_coord, int NB)
+{
+    extern __shared__ float s_sum[];            // [4][NB]
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int c = blockIdx.x * kSdCoords + tid;
+    const bool live = c < n_coord;
+    const float xv = live ? x[(size_t)b * n_coord + c] : 0.f;
+    const float* row = dirs + (size_t)(live ? c : 0) * NB;
+    for (int k = 0; k < NB; ++k) {
+        float a = live ? row[k] * xv : 0.f;
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if ((tid & 63) == 0) s_sum[(tid >> 6) * NB + k] = a;
+    }
+    __syncthreads();
+    float* slab = slabs + ((size_t)blockIdx.x * gridDim.y + b) * NB;
+    for (int k = tid; k < NB; k += kSdCoords) slab[k] = (s_sum[k] + s_sum[NB + k]) + (s_sum[2 * NB + k] + s_sum[3 * NB + k]);
+}
+
 static bool model_ok(const AgSmplxModel* m)
 {
     return m && m->V > 0 && m->J > 0 && m->J <= kMaxJoints && m->NB >= 0 && m->NB <= 4096 && m->v_template && m->posedirs &&
@@ -540,14 +770,14 @@ static bool folded_ok(const AgSmplxModel* m)
 
 template <int NBATCH>
 static void launch_skin(const AgSmplxModel* m, float* vertices, const float* feat, const float* v_shaped, const float* A,
-                        const float* transl, hipStream_t s)
+                        const float* transl, float* v_posed, hipStream_t s)
 {
     const int P = 9 * (m->J - 1);
     const size_t lds = sizeof(float) * ((size_t)NBATCH * P + (size_t)NBATCH * m->J * 12 + (size_t)kSkinSlices * NBATCH * kSkinCoords +
                                         (size_t)NBATCH * kSkinCoords);
     const int grid = (m->V + kSkinVerts - 1) / kSkinVerts;
     hipLaunchKernelGGL(smplx_skin_kernel<NBATCH>, dim3(grid), dim3(kSkinThreads), lds, s, vertices, m->posedirs, feat, v_shaped, A,
-                       m->lbs_weights, transl, m->V, m->J, P);
+                       m->lbs_weights, transl, v_posed, m->V, m->J, P);
 }
 
 }  // namespace ag
@@ -562,8 +792,10 @@ size_t ag_smplx_workspace_floats(const AgSmplxModel* m, int32_t B)
     return (size_t)B * ((size_t)3 * m->V + (size_t)12 * m->J + (size_t)9 * (m->J - 1));
 }
 
-int ag_smplx_forward(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* transl,
-                     float* vertices, float* joints, float* A, float* workspace, size_t workspace_floats, void* stream)
+// ag_smplx_forward and ag_smplx_forward_keep: the same three launches; `saved` (NULL: nothing kept) receives v_posed from the skin
+// kernel and takes the place of the workspace's A_skin block.
+static int smplx_forward_impl(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* transl,
+                              float* vertices, float* joints, float* A, float* workspace, size_t workspace_floats, float* saved, void* stream)
 {
     if (!model_ok(m)) { set_error("smplx: bad model (need 0 < J <= 64, non-null arrays)"); return AG_ERR_INVALID_ARGUMENT; }
     if (!folded_ok(m)) { set_error("smplx: joint_template / joint_dirs missing -- run ag_smplx_prepare once per model"); return AG_ERR_INVALID_ARGUMENT; }
@@ -577,8 +809,8 @@ int ag_smplx_forward(const AgSmplxModel* m, int32_t B, const float* shape_compon
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n_coord = 3 * m->V, P = 9 * (m->J - 1);
     float* v_shaped = workspace;
-    float* A_skin = v_shaped + (size_t)B * n_coord;
-    float* feat = A_skin + (size_t)B * 12 * m->J;
+    float* A_skin = saved ? saved + (size_t)B * n_coord : v_shaped + (size_t)B * n_coord;
+    float* feat = v_shaped + (size_t)B * n_coord + (size_t)B * 12 * m->J;
 
     hipLaunchKernelGGL(smplx_shape_kernel, dim3((n_coord + 255) / 256, B), dim3(256), sizeof(float) * (m->NB > 0 ? m->NB : 1), s, v_shaped,
                        m->v_template, m->shapedirs, shape_components, n_coord, m->NB);
@@ -591,14 +823,38 @@ int ag_smplx_forward(const AgSmplxModel* m, int32_t B, const float* shape_compon
         const float* vs = v_shaped + (size_t)b0 * n_coord;
         const float* Ab = A_skin + (size_t)b0 * m->J * 12;
         const float* tb = transl ? transl + (size_t)3 * b0 : nullptr;
+        float* vp = saved ? saved + (size_t)b0 * n_coord : nullptr;
         switch (nb) {
-            case 1: launch_skin<1>(m, vo, f, vs, Ab, tb, s); break;
-            case 2: launch_skin<2>(m, vo, f, vs, Ab, tb, s); break;
-            case 3: launch_skin<3>(m, vo, f, vs, Ab, tb, s); break;
-            default: launch_skin<4>(m, vo, f, vs, Ab, tb, s); break;
+            case 1: launch_skin<1>(m, vo, f, vs, Ab, tb, vp, s); break;
+            case 2: launch_skin<2>(m, vo, f, vs, Ab, tb, vp, s); break;
+            case 3: launch_skin<3>(m, vo, f, vs, Ab, tb, vp, s); break;
+            default: launch_skin<4>(m, vo, f, vs, Ab, tb, vp, s); break;
         }
     }
     return check_hip(hipGetLastError(), "ag_smplx_forward");
+}
+
+int ag_smplx_forward(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* transl,
+                     float* vertices, float* joints, float* A, float* workspace, size_t workspace_floats, void* stream)
+{
+    return smplx_forward_impl(m, B, shape_components, full_pose, transl, vertices, joints, A, workspace, workspace_floats, nullptr, stream);
+}
+
+size_t ag_smplx_saved_floats(const AgSmplxModel* m, int32_t B)
+{
+    if (!m || B <= 0) return 0;
+    return (size_t)B * ((size_t)3 * m->V + (size_t)12 * m->J);
+}
+
+int ag_smplx_forward_keep(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* transl,
+                          float* vertices, float* joints, float* A, float* workspace, size_t workspace_floats, float* saved,
+                          size_t saved_floats, void* stream)
+{
+    if (B > 0 && (!saved || !m || saved_floats < ag_smplx_saved_floats(m, B))) {
+        set_error("smplx_forward_keep: `saved` missing or smaller than ag_smplx_saved_floats");
+        return AG_ERR_INVALID_ARGUMENT;
+    }
+    return smplx_forward_impl(m, B, shape_components, full_pose, transl, vertices, joints, A, workspace, workspace_floats, saved, stream);
 }
 
 int ag_smplx_prepare(const AgSmplxModel* m, float* joint_template, float* joint_dirs, void* stream)
@@ -640,9 +896,9 @@ int ag_smplx_backward(const AgSmplxModel* m, int32_t B, const float* shape_compo
     if (B < 0) { set_error("smplx_backward: B < 0"); return AG_ERR_INVALID_ARGUMENT; }
     if (B == 0) return AG_OK;
     if (!full_pose || !dL_dfull_pose || (m->NB > 0 && !shape_components)) { set_error("smplx_backward: null pointer"); return AG_ERR_INVALID_ARGUMENT; }
-    hipLaunchKernelGGL(smplx_chain_backward_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), dL_dfull_pose, dL_dtransl,
+    hipLaunchKernelGGL(smplx_chain_backward_kernel<false>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), dL_dfull_pose, dL_dtransl,
                        m->NB > 0 ? dL_dshape_components : nullptr, dL_dA, dL_djoints, full_pose, shape_components, m->joint_template,
-                       m->joint_dirs, m->parents, m->J, m->NB);
+                       m->joint_dirs, m->parents, m->J, m->NB, nullptr, nullptr, nullptr, nullptr);
     return check_hip(hipGetLastError(), "smplx_chain_backward_kernel");
 }
 
@@ -666,6 +922,117 @@ int ag_smplx_keypoints(float* out, const float* vertices, const int32_t* idx, co
     hipLaunchKernelGGL(smplx_keypoints_kernel, dim3((3 * K + 63) / 64, B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), out, vertices,
                        idx, w, V, K);
     return check_hip(hipGetLastError(), "smplx_keypoints_kernel");
+}
+
+int ag_smplx_keypoints_backward(float* dL_dvertices, const float* dL_dkeypoints, const int32_t* idx, const float* w, int32_t B, int32_t V,
+                                int32_t K, void* stream)
+{
+    if (B < 0 || K < 0 || K > 1024 || V <= 0) { set_error("smplx_keypoints_backward: bad sizes (need K <= 1024)"); return AG_ERR_INVALID_ARGUMENT; }
+    if (B == 0) return AG_OK;
+    if (!dL_dvertices || (K > 0 && (!dL_dkeypoints || !idx || !w))) { set_error("null pointer"); return AG_ERR_INVALID_ARGUMENT; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = check_hip(hipMemsetAsync(dL_dvertices, 0, (size_t)B * V * 3 * sizeof(float), s), "smplx_keypoints_backward: memset");
+    if (rc != AG_OK || K == 0) return rc;
+    hipLaunchKernelGGL(smplx_keypoints_backward_kernel, dim3(B), dim3(256), sizeof(float) * 9 * K, s, dL_dvertices, dL_dkeypoints, idx, w, V, K);
+    return check_hip(hipGetLastError(), "smplx_keypoints_backward_kernel");
+}
+
+static size_t vb_skin_slabs(const AgSmplxModel* m) { return (size_t)(m->V + kVbVerts - 1) / kVbVerts; }
+static size_t vb_dirs_slabs(const AgSmplxModel* m) { return (size_t)(3 * m->V + kSdCoords - 1) / kSdCoords; }
+
+size_t ag_smplx_vertex_backward_workspace_floats(const AgSmplxModel* m, int32_t B)
+{
+    if (!m || B <= 0 || m->V <= 0 || m->J <= 0 || m->NB < 0) return 0;
+    // dL/dv_posed | skinning slabs | shape-basis slabs
+    return (size_t)B * ((size_t)3 * m->V + vb_skin_slabs(m) * ((size_t)12 * m->J + 3) + vb_dirs_slabs(m) * (size_t)m->NB);
+}
+
+// slabs [n_slab][B][NB] of smplx_dirs_t_kernel over x [B][3 V]
+static void launch_dirs_t(const AgSmplxModel* m, int32_t B, const float* x, float* slabs, hipStream_t s)
+{
+    hipLaunchKernelGGL(smplx_dirs_t_kernel, dim3((unsigned)vb_dirs_slabs(m), B), dim3(kSdCoords), sizeof(float) * 4 * m->NB, s, slabs, m->shapedirs,
+                       x, 3 * m->V, m->NB);
+}
+
+int ag_smplx_vertex_backward(const AgSmplxModel* m, int32_t B, const float* saved, const float* dL_dvertices, float* dL_dA_skin,
+                             float* dL_dfeat, float* dL_dtransl, float* dL_dshape_components, float* workspace, size_t workspace_floats,
+                             void* stream)
+{
+    if (!model_ok(m)) { set_error("smplx_vertex_backward: bad model (need 0 < J <= 64, non-null arrays)"); return AG_ERR_INVALID_ARGUMENT; }
+    if (B < 0) { set_error("smplx_vertex_backward: B < 0"); return AG_ERR_INVALID_ARGUMENT; }
+    if (B == 0) return AG_OK;
+    if (!saved || !dL_dvertices || !dL_dA_skin || !dL_dtransl || !workspace || (m->J > 1 && !dL_dfeat) || (m->NB > 0 && !dL_dshape_components)) {
+        set_error("smplx_vertex_backward: null pointer");
+        return AG_ERR_INVALID_ARGUMENT;
+    }
+    if (workspace_floats < ag_smplx_vertex_backward_workspace_floats(m, B)) { set_error("smplx_vertex_backward: workspace too small"); return AG_ERR_SCRATCH_TOO_SMALL; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int n_coord = 3 * m->V, P = 9 * (m->J - 1), J = m->J;
+    const int n_slab = (int)vb_skin_slabs(m), width = 12 * J + 3;
+    const float* v_posed = saved;
+    const float* A_skin = saved + (size_t)B * n_coord;
+    float* dvp = workspace;
+    float* skin_slabs = dvp + (size_t)B * n_coord;
+    float* dirs_slabs = skin_slabs + (size_t)n_slab * B * width;
+
+    const size_t lds = sizeof(float) * ((size_t)kVbVerts * J + (size_t)J * 12 + 8 * kVbVerts);
+    hipLaunchKernelGGL(smplx_skin_backward_kernel, dim3(n_slab, B), dim3(kVbThreads), lds, s, dvp, skin_slabs, dL_dvertices, v_posed, A_skin,
+                       m->lbs_weights, m->V, J);
+    const int dirs_total = B * m->NB, n_skin_blocks = (B * width + 15) / 16;
+    if (m->NB > 0) launch_dirs_t(m, B, dvp, dirs_slabs, s);
+    hipLaunchKernelGGL(smplx_slab_sums_kernel, dim3(n_skin_blocks + (dirs_total + 15) / 16), dim3(256), 0, s, dL_dA_skin, dL_dtransl, skin_slabs,
+                       n_slab, B, J, n_skin_blocks, dL_dshape_components, dirs_slabs, (int)vb_dirs_slabs(m), dirs_total);
+    if (P > 0)
+        for (int b0 = 0; b0 < B; b0 += 4) {
+            const int nb = B - b0 < 4 ? B - b0 : 4;
+            float* df = dL_dfeat + (size_t)b0 * P;
+            const float* x = dvp + (size_t)b0 * n_coord;
+            switch (nb) {
+                case 1: hipLaunchKernelGGL(smplx_posedirs_t_kernel<1>, dim3(P), dim3(kPdThreads), 0, s, df, m->posedirs, x, n_coord, P); break;
+                case 2: hipLaunchKernelGGL(smplx_posedirs_t_kernel<2>, dim3(P), dim3(kPdThreads), 0, s, df, m->posedirs, x, n_coord, P); break;
+                case 3: hipLaunchKernelGGL(smplx_posedirs_t_kernel<3>, dim3(P), dim3(kPdThreads), 0, s, df, m->posedirs, x, n_coord, P); break;
+                default: hipLaunchKernelGGL(smplx_posedirs_t_kernel<4>, dim3(P), dim3(kPdThreads), 0, s, df, m->posedirs, x, n_coord, P); break;
+            }
+        }
+    return check_hip(hipGetLastError(), "ag_smplx_vertex_backward");
+}
+
+size_t ag_smplx_shape_backward_workspace_floats(const AgSmplxModel* m, int32_t B)
+{
+    if (!m || B <= 0 || m->V <= 0 || m->NB < 0) return 0;
+    return (size_t)B * vb_dirs_slabs(m) * (size_t)m->NB;
+}
+
+int ag_smplx_shape_backward(const AgSmplxModel* m, int32_t B, const float* dL_dv_shaped, float* dL_dshape_components, float* workspace,
+                            size_t workspace_floats, void* stream)
+{
+    if (!model_ok(m) || B < 0) { set_error("smplx_shape_backward: bad model or B < 0"); return AG_ERR_INVALID_ARGUMENT; }
+    if (B == 0 || m->NB == 0) return AG_OK;
+    if (!dL_dv_shaped || !dL_dshape_components || !workspace) { set_error("smplx_shape_backward: null pointer"); return AG_ERR_INVALID_ARGUMENT; }
+    if (workspace_floats < ag_smplx_shape_backward_workspace_floats(m, B)) { set_error("smplx_shape_backward: workspace too small"); return AG_ERR_SCRATCH_TOO_SMALL; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int dirs_total = B * m->NB;
+    launch_dirs_t(m, B, dL_dv_shaped, workspace, s);
+    hipLaunchKernelGGL(smplx_slab_sums_kernel, dim3((dirs_total + 15) / 16), dim3(256), 0, s, (float*)nullptr, (float*)nullptr, (const float*)nullptr,
+                       0, B, m->J, 0, dL_dshape_components, workspace, (int)vb_dirs_slabs(m), dirs_total);
+    return check_hip(hipGetLastError(), "ag_smplx_shape_backward");
+}
+
+int ag_smplx_backward_full(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* dL_dA,
+                           const float* dL_djoints, const float* dL_dA_skin, const float* dL_dfeat, const float* dL_dtransl_add,
+                           const float* dL_dshape_components_add, float* dL_dfull_pose, float* dL_dtransl, float* dL_dshape_components,
+                           void* stream)
+{
+    if (!model_ok(m)) { set_error("smplx_backward_full: bad model (need 0 < J <= 64, non-null arrays)"); return AG_ERR_INVALID_ARGUMENT; }
+    if (!folded_ok(m)) { set_error("smplx_backward_full: joint_template / joint_dirs missing -- run ag_smplx_prepare once per model"); return AG_ERR_INVALID_ARGUMENT; }
+    if (B < 0) { set_error("smplx_backward_full: B < 0"); return AG_ERR_INVALID_ARGUMENT; }
+    if (B == 0) return AG_OK;
+    if (!full_pose || !dL_dfull_pose || (m->NB > 0 && !shape_components)) { set_error("smplx_backward_full: null pointer"); return AG_ERR_INVALID_ARGUMENT; }
+    hipLaunchKernelGGL(smplx_chain_backward_kernel<true>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), dL_dfull_pose, dL_dtransl,
+                       m->NB > 0 ? dL_dshape_components : nullptr, dL_dA, dL_djoints, full_pose, shape_components, m->joint_template,
+                       m->joint_dirs, m->parents, m->J, m->NB, dL_dA_skin, dL_dfeat, dL_dtransl_add,
+                       m->NB > 0 ? dL_dshape_components_add : nullptr);
+    return check_hip(hipGetLastError(), "smplx_chain_backward_kernel");
 }
 
 }  // extern "C"

@@ -10,9 +10,14 @@ once for the whole batch.  ``data_item`` is the three-call pattern of the datase
 
 ``forward`` is differentiable, as the reference's torch model is, for the outputs ``A`` and ``joints[:, :55]`` (the kinematic chain:
 ``ag_smplx_backward``) with respect to ``betas``, ``expression``, every pose argument and ``transl``; ``mat4_mul_inverse`` is
-differentiable in both operands.  The vertices and the vertex key points ``joints[:, 55:]`` have no backward: a non-zero gradient
-that reaches them raises ``NotImplementedError``.  ``data_item`` (the dataset path) runs without autograd, as the reference's
-dataset does (dataset_mv_rgb.py:118).  float32; there is no CPU path.
+differentiable in both operands.  By default the vertices and the vertex key points ``joints[:, 55:]`` have no backward (a non-zero
+gradient that reaches them raises ``NotImplementedError``) and ``v_shaped`` is produced outside autograd.  ``SMPLX(...,
+vertex_grad=True)`` differentiates those too -- ``vertices``, all 127 ``joints`` and ``v_shaped``, what key-point, vertex and shape
+fitting losses are written on -- with the same forward launches and bits: the skinning backward, the transposed pose-corrective and
+shape bases (``ag_smplx_vertex_backward``, the 61-MB basis again read once per call) and the key-point scatter
+(``ag_smplx_keypoints_backward``) feed the chain backward (``ag_smplx_backward_full``).  Every sum has a fixed order: the same inputs
+give the same gradient bits.  ``data_item`` (the dataset path) runs without autograd, as the reference's dataset does
+(dataset_mv_rgb.py:118).  float32; there is no CPU path.
 The vertex ids of the 21 extra joints are SMPL-X model-topology constants (smplx/vertex_ids.py:49-72).
 """
 from __future__ import annotations
@@ -107,21 +112,29 @@ def mat4_mul_inverse(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 
 class _SmplxLbs(torch.autograd.Function):
-    """(shape components, full pose, transl) -> (vertices, joints [B,J,3], A); backward for joints and A only (ag_smplx_backward)."""
+    """(shape components, full pose, transl) -> (vertices, joints [B,J,3], A); backward for joints and A (ag_smplx_backward) and, on a
+    ``vertex_grad`` model, for the vertices (ag_smplx_vertex_backward -> ag_smplx_backward_full)."""
 
     @staticmethod
     def forward(ctx, model, comps, pose, transl):
         ctx.set_materialize_grads(False)
-        verts, joints, A = model._lbs_launch(comps, pose, transl)
-        ctx.model, ctx.has_transl = model, transl is not None
-        ctx.save_for_backward(comps, pose)
+        ctx.model, ctx.has_transl, ctx.vertex_grad = model, transl is not None, model.vertex_grad
+        if ctx.vertex_grad:
+            verts, joints, A, saved = model._lbs_launch(comps, pose, transl, keep=True)
+            ctx.save_for_backward(comps, pose, saved)
+        else:
+            verts, joints, A = model._lbs_launch(comps, pose, transl)
+            ctx.save_for_backward(comps, pose)
         return verts, joints, A
 
     @staticmethod
     def backward(ctx, g_verts, g_joints, g_A):
-        if g_verts is not None and bool(g_verts.ne(0).any()):
+        if ctx.vertex_grad:
+            if g_verts is not None:
+                return _SmplxLbs._backward_with_vertices(ctx, g_verts, g_joints, g_A)
+        elif g_verts is not None and bool(g_verts.ne(0).any()):
             raise NotImplementedError("SMPLX: the vertices have no backward (only A and joints[:, :55], the kinematic chain, do)")
-        comps, pose = ctx.saved_tensors
+        comps, pose = ctx.saved_tensors[:2]
         model = ctx.model
         m = model._model()
         B, dev = pose.shape[0], pose.device
@@ -135,15 +148,70 @@ class _SmplxLbs(torch.autograd.Function):
                                                     _stream(dev)), "ag_smplx_backward")
         return None, dcomps, dpose, dtr
 
+    @staticmethod
+    def _backward_with_vertices(ctx, g_verts, g_joints, g_A):
+        comps, pose, saved = ctx.saved_tensors
+        model = ctx.model
+        m = model._model()
+        B, dev = pose.shape[0], pose.device
+        L = _lib.lib()
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        dAs, dfeat, dtr_v = f32(B, m.J, 12), f32(B, max(9 * (m.J - 1), 1)), f32(B, 3)
+        dcomps_v = f32(B, m.NB) if m.NB > 0 else None
+        nws = L.ag_smplx_vertex_backward_workspace_floats(ctypes.byref(m), B)
+        ws = f32(max(nws, 1))
+        dpose = torch.empty_like(pose)
+        dcomps = torch.empty_like(comps) if m.NB > 0 else None
+        want_tr = ctx.has_transl and ctx.needs_input_grad[3]
+        dtr = f32(B, 3) if want_tr else None
+        gV = g_verts.contiguous()
+        gA = g_A.contiguous() if g_A is not None else None
+        gJ = g_joints.contiguous() if g_joints is not None else None
+        with torch.cuda.device(dev):
+            _lib.check(L.ag_smplx_vertex_backward(ctypes.byref(m), B, _p(saved), _p(gV), _p(dAs), _p(dfeat), _p(dtr_v), _p(dcomps_v), _p(ws), nws,
+                                                  _stream(dev)), "ag_smplx_vertex_backward")
+            _lib.check(L.ag_smplx_backward_full(ctypes.byref(m), B, _p(comps), _p(pose), _p(gA), _p(gJ), _p(dAs), _p(dfeat) if m.J > 1 else None,
+                                                _p(dtr_v), _p(dcomps_v), _p(dpose), _p(dtr), _p(dcomps), _stream(dev)), "ag_smplx_backward_full")
+        return None, dcomps, dpose, dtr
+
+
+class _SmplxShape(torch.autograd.Function):
+    """v_shaped of ag_smplx_shape on a ``vertex_grad`` model; backward: the transposed shape basis (ag_smplx_shape_backward)."""
+
+    @staticmethod
+    def forward(ctx, model, comps):
+        ctx.model = model
+        m = model._model()
+        B, dev = comps.shape[0], model.v_template.device
+        v_shaped = torch.empty((B, m.V, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ag_smplx_shape(ctypes.byref(m), B, _p(comps), _p(v_shaped), _stream(dev)), "ag_smplx_shape")
+        return v_shaped
+
+    @staticmethod
+    def backward(ctx, g):
+        m = ctx.model._model()
+        B, dev = g.shape[0], g.device
+        L = _lib.lib()
+        dcomps = torch.zeros((B, m.NB), dtype=torch.float32, device=dev)
+        nws = L.ag_smplx_shape_backward_workspace_floats(ctypes.byref(m), B)
+        ws = torch.empty((max(nws, 1),), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.ag_smplx_shape_backward(ctypes.byref(m), B, _p(g.contiguous()), _p(dcomps), _p(ws), nws, _stream(dev)),
+                       "ag_smplx_shape_backward")
+        return None, dcomps
+
 
 class _Keypoints(torch.autograd.Function):
-    """The barycentric vertex key points (ag_smplx_keypoints); no backward: a non-zero gradient that reaches them raises."""
+    """The barycentric vertex key points (ag_smplx_keypoints).  Default model: no backward, a non-zero gradient that reaches them raises;
+    ``vertex_grad`` model: the scatter to the vertices (ag_smplx_keypoints_backward)."""
 
     @staticmethod
     def forward(ctx, model, verts):
         ctx.set_materialize_grads(False)
         B, dev = verts.shape[0], verts.device
         K = model._kp_idx.shape[0]
+        ctx.model, ctx.shape = model, (B, verts.shape[1])
         extra = torch.empty((B, K, 3), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().ag_smplx_keypoints(_p(extra), _p(verts), _p(model._kp_idx), _p(model._kp_w), B, verts.shape[1], K,
@@ -152,6 +220,16 @@ class _Keypoints(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        model = ctx.model
+        if model.vertex_grad:
+            if g is None:
+                return None, None
+            B, V = ctx.shape
+            dverts = torch.empty((B, V, 3), dtype=torch.float32, device=g.device)
+            with torch.cuda.device(g.device):
+                _lib.check(_lib.lib().ag_smplx_keypoints_backward(_p(dverts), _p(g.contiguous()), _p(model._kp_idx), _p(model._kp_w), B, V,
+                                                                  model._kp_idx.shape[0], _stream(g.device)), "ag_smplx_keypoints_backward")
+            return None, dverts
         if g is not None and bool(g.ne(0).any()):
             raise NotImplementedError("SMPLX: the vertex key points joints[:, 55:] (extra vertex joints and face landmarks) have no backward")
         return None, None
@@ -167,10 +245,17 @@ class SMPLX(nn.Module):
 
     def __init__(self, model_path, gender: str = 'neutral', use_pca: bool = True, num_pca_comps: int = 6, flat_hand_mean: bool = False,
                  batch_size: int = 1, num_betas: int = 10, num_expression_coeffs: int = 10, ext: str = 'npz', device='cuda',
-                 use_face_contour: bool = False, dtype=torch.float32, **kwargs):
+                 use_face_contour: bool = False, dtype=torch.float32, vertex_grad: bool = False, **kwargs):
         """``model_path``: the directory holding ``SMPLX_{GENDER}.npz`` or the file itself (body_models.py:967-979), or a dict
-        of its arrays.  use_pca / face contour are not built (the reference passes use_pca=False everywhere)."""
+        of its arrays.  use_pca / face contour are not built (the reference passes use_pca=False everywhere).
+
+        ``vertex_grad``: also differentiate ``vertices``, the vertex key points ``joints[:, 55:]`` and ``v_shaped`` (with respect to
+        ``betas``, ``expression``, every pose argument and ``transl``; gradients from several outputs add up).  Forward values do not
+        depend on it.  It is opt-in, and ``False`` keeps the earlier behaviour bit for bit, because that behaviour -- a gradient
+        reaching those outputs raises ``NotImplementedError``, ``v_shaped`` carries no graph -- is pinned by the test suite on a
+        default-constructed model; a ``True`` model keeps B x (3 V + 12 J) floats per forward for its backward."""
         super().__init__()
+        self.vertex_grad = bool(vertex_grad)
         if use_pca:
             raise NotImplementedError("SMPLX(use_pca=True): the reference constructs every model with use_pca=False")
         if use_face_contour:
@@ -274,7 +359,7 @@ class SMPLX(nn.Module):
 
     def lbs(self, shape_components: torch.Tensor, full_pose: torch.Tensor, transl: Optional[torch.Tensor]):
         """(vertices [B,V,3], posed joints [B,J,3], A [B,J,4,4]) of smplx/lbs.py:152-246 (+ body_models.py:1272-1275).
-        Differentiable for joints and A (``_SmplxLbs``)."""
+        Differentiable for joints and A, and for the vertices on a ``vertex_grad`` model (``_SmplxLbs``)."""
         dev = self.v_template.device
         m = self._model()
         B = full_pose.shape[0]
@@ -285,7 +370,7 @@ class SMPLX(nn.Module):
             raise RuntimeError(f"shape components {tuple(comps.shape)} != ({B}, {m.NB})")
         return _SmplxLbs.apply(self, comps, pose, tr)
 
-    def _lbs_launch(self, comps, pose, tr):
+    def _lbs_launch(self, comps, pose, tr, keep: bool = False):
         dev = self.v_template.device
         m = self._model()
         B = pose.shape[0]
@@ -295,6 +380,13 @@ class SMPLX(nn.Module):
         L = _lib.lib()
         nws = L.ag_smplx_workspace_floats(ctypes.byref(m), B)
         ws = torch.empty((max(nws, 1),), dtype=torch.float32, device=dev)
+        if keep:        # the same launches; v_posed and the skinning matrices stay for ag_smplx_vertex_backward
+            nsv = L.ag_smplx_saved_floats(ctypes.byref(m), B)
+            saved = torch.empty((max(nsv, 1),), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(L.ag_smplx_forward_keep(ctypes.byref(m), B, _p(comps), _p(pose), _p(tr), _p(verts), _p(joints), _p(A), _p(ws), nws,
+                                                   _p(saved), nsv, _stream(dev)), "ag_smplx_forward_keep")
+            return verts, joints, A, saved
         with torch.cuda.device(dev):
             _lib.check(L.ag_smplx_forward(ctypes.byref(m), B, _p(comps), _p(pose), _p(tr), _p(verts), _p(joints), _p(A), _p(ws), nws,
                                           _stream(dev)), "ag_smplx_forward")
@@ -332,10 +424,13 @@ class SMPLX(nn.Module):
         v_shaped = None
         if return_shaped:                                                              # body_models.py:1277-1279 (betas only)
             only_betas = torch.cat([betas, torch.zeros_like(expression)], -1).contiguous()
-            v_shaped = torch.empty_like(verts)
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib().ag_smplx_shape(ctypes.byref(self._model()), B, _p(only_betas), _p(v_shaped), _stream(dev)),
-                           "ag_smplx_shape")
+            if self.vertex_grad:
+                v_shaped = _SmplxShape.apply(self, only_betas)
+            else:
+                v_shaped = torch.empty_like(verts)
+                with torch.cuda.device(dev):
+                    _lib.check(_lib.lib().ag_smplx_shape(ctypes.byref(self._model()), B, _p(only_betas), _p(v_shaped), _stream(dev)),
+                               "ag_smplx_shape")
         return SMPLXOutput(vertices=verts if return_verts else None, joints=joints, betas=betas, expression=expression,
                            global_orient=global_orient, body_pose=body_pose, left_hand_pose=left_hand_pose,
                            right_hand_pose=right_hand_pose, jaw_pose=jaw_pose, v_shaped=v_shaped, transl=transl,

@@ -514,6 +514,39 @@ def pose_grad_bench(dev, steps, warmup):
             "loss_first": float(losses[0]), "loss_last": float(losses[-1])}
 
 
+def smplx_fit_bench(dev, steps, warmup):
+    """ms per iteration of an SMPL-X fit on a ``vertex_grad`` model: forward -> mean squared distance over the 72 vertex key points
+    joints[:, 55:] plus the same over the 10 475 vertices -> backward to betas, expression, global_orient, body_pose, jaw_pose, both
+    hand poses and transl -> Adam (lr 0.02), from all-zero parameters.  Synthetic SMPL-X model (V = 10 475, J = 55), one pose."""
+    import torch
+    from animatablegaussians_amd import synth
+    from animatablegaussians_amd.smplx import SMPLX
+    smplx = SMPLX(synth.smplx_model_arrays(), gender='neutral', use_pca=False, flat_hand_mean=True, device=dev, vertex_grad=True)
+    sizes = {"betas": 10, "expression": 10, "global_orient": 3, "body_pose": 63, "jaw_pose": 3, "left_hand_pose": 45, "right_hand_pose": 45,
+             "transl": 3}
+    g = torch.Generator().manual_seed(31359)
+    truth = {k: (torch.randn(1, n, generator=g) * (1.0 if k in ("betas", "expression") else 0.3)).to(dev) for k, n in sizes.items()}
+    with torch.no_grad():
+        t = smplx(**truth)
+        target_kp, target_v = t.joints[:, 55:].clone(), t.vertices.clone()
+    x = {k: torch.zeros(1, n, device=dev, requires_grad=True) for k, n in sizes.items()}
+    opt = torch.optim.Adam(list(x.values()), lr=0.02)
+    losses = []
+
+    def step(_i):
+        opt.zero_grad(set_to_none=True)
+        out = smplx(**x)
+        loss = (out.joints[:, 55:] - target_kp).square().sum(-1).mean() + (out.vertices - target_v).square().sum(-1).mean()
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+
+    ms = timed_median(step, steps, warmup, dev)
+    return {"metric": "SMPL-X fit iteration (forward + key-point and vertex loss + backward to 8 parameter groups + Adam) ms, B = 1",
+            "ms_per_iter": ms, "vertices": int(smplx.v_template.shape[0]), "steps": steps, "warmup": warmup,
+            "loss_first": float(losses[0]), "loss_last": float(losses[-1])}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -531,6 +564,8 @@ def main() -> None:
                     "views of one pose: no pose-shared work is replicated, the job scales weakly (DESIGN.md section 6, mode (b))")
     ap.add_argument("--pose-grad", action="store_true", help="only time test-time pose refinement: SMPL-X -> mat4_mul_inverse -> get_pose_map -> "
                     "render -> L1 -> backward -> Adam on body_pose (eval mode, frozen weights, synthetic subject, 1024^2)")
+    ap.add_argument("--smplx-fit", action="store_true", help="only time an SMPL-X fit iteration on a vertex_grad model: forward -> key-point + "
+                    "vertex loss -> backward to shape, expression, poses and transl -> Adam (synthetic model, one pose)")
     args = ap.parse_args()
 
     import torch
@@ -551,6 +586,9 @@ def main() -> None:
         return
     if args.pose_grad:
         print(json.dumps(pose_grad_bench(dev, args.steps, args.warmup)), flush=True)
+        return
+    if args.smplx_fit:
+        print(json.dumps(smplx_fit_bench(dev, args.steps, args.warmup)), flush=True)
         return
 
     ts = TrainingStep(dev, viewdirs=not args.no_viewdirs, lpips=args.lpips and not args.infer, world=world, rank=rank, pose_per_rank=args.pose_per_rank)

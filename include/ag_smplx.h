@@ -88,6 +88,69 @@ int ag_mat4_mul_inverse_backward(float* dL_da, float* dL_db, const float* dL_dou
  * out[b][k] = sum_t w[k][t] * vertices[b][idx[k][t]], t < 3.  idx [K][3] int32, w [K][3]. */
 int ag_smplx_keypoints(float* out, const float* vertices, const int32_t* idx, const float* w, int32_t B, int32_t V, int32_t K, void* stream);
 
+/*
+ * The backward of the vertex path: `vertices`, the vertex key points and `v_shaped`.  Notation of lbs.py:223-246:
+ *   v_posed = v_shaped + pose_feature . posedirs;  T_v = sum_j W[v][j] A_skin[j]  (A_skin: A before `transl` is added);
+ *   vertices = T_v[:3,:3] v_posed + T_v[:3,3] (+ transl).
+ * Five additive entry points; ag_smplx_forward and ag_smplx_backward keep their signatures and their bits.  No float atomics anywhere:
+ * every sum below has a fixed order, two calls give the same bits.
+ */
+
+/* Floats of `saved` that ag_smplx_forward_keep fills for B poses: v_posed [B][V][3] | A_skin [B][J][12] (rows 0-2 of the 4x4). */
+size_t ag_smplx_saved_floats(const AgSmplxModel* m, int32_t B);
+
+/* ag_smplx_forward (same arguments, same three launches, same output bits) that also keeps what ag_smplx_vertex_backward reads, so that
+ * the 61-MB basis is not streamed a second time to rebuild v_posed.  saved: device floats, at least ag_smplx_saved_floats(m, B). */
+int ag_smplx_forward_keep(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* transl,
+                          float* vertices, float* joints, float* A, float* workspace, size_t workspace_floats, float* saved,
+                          size_t saved_floats, void* stream);
+
+/* Backward of ag_smplx_keypoints (vertex_joint_selector.py:72-76, lbs.py:108-149) with respect to the vertices:
+ * dL_dvertices [B][V][3] is ZEROED by the call, then dL_dvertices[b][idx[k][t]] += w[k][t] dL_dkeypoints[b][k].  Vertex ids may repeat
+ * (landmark triangles share vertices): the first entry (k, t) that names a vertex gathers every entry with the same id in ascending
+ * 3 k + t and stores once.  Ids outside [0, V) are skipped.  K <= 1024.  No pointer may be NULL unless K = 0. */
+int ag_smplx_keypoints_backward(float* dL_dvertices, const float* dL_dkeypoints, const int32_t* idx, const float* w, int32_t B, int32_t V,
+                                int32_t K, void* stream);
+
+/* Floats of workspace ag_smplx_vertex_backward needs (dL/dv_posed, one slab per 64 vertices, one slab per 256 coordinates). */
+size_t ag_smplx_vertex_backward_workspace_floats(const AgSmplxModel* m, int32_t B);
+
+/*
+ * Backward of lbs.py:223-246 (+ body_models.py:1274) for g = dL_dvertices [B][V][3], from `saved` of ag_smplx_forward_keep:
+ *   dL/dv_posed[v] = T_v[:3,:3]^T g[v]                                                       (kept in the workspace)
+ *   dL_dA_skin [B][J][12]   = sum_v W[v][j] g[v] (x) [v_posed[v]; 1]      hand to ag_smplx_backward_full
+ *   dL_dtransl [B][3]       = sum_v g[v]                                   (the same whether or not the forward had a transl)
+ *   dL_dfeat [B][9 (J-1)]   = posedirs . dL/dv_posed                       (lbs.py:223 transposed; may be NULL only when J = 1)
+ *   dL_dshape_components [B][NB] = shapedirs^T . dL/dv_posed               (lbs.py:208 transposed, the DIRECT term: v_shaped enters v_posed;
+ *                                                                           the path through the rest joints is ag_smplx_backward_full's)
+ * All outputs are overwritten.  Order of the sums: over vertices, 64 consecutive vertices in ascending order per slab, then the slabs
+ * in 16 running sums (slab index mod 16, each ascending) added in ascending order of the remainder; over the 3 V coordinates of a
+ * posedirs row (read once for up to four poses), 1024 running sums (coordinate mod 1024, ascending), then lanes by xor-shuffle 32, 16,
+ * .. 1, then the 16 waves in ascending order; over the coordinates for the shape basis, 256 per slab (lanes by xor-shuffle, four waves
+ * as (w0 + w1) + (w2 + w3)), then the slabs as above.
+ */
+int ag_smplx_vertex_backward(const AgSmplxModel* m, int32_t B, const float* saved, const float* dL_dvertices, float* dL_dA_skin,
+                             float* dL_dfeat, float* dL_dtransl, float* dL_dshape_components, float* workspace, size_t workspace_floats,
+                             void* stream);
+
+/* Backward of ag_smplx_shape: dL_dshape_components [B][NB] = shapedirs^T . dL_dv_shaped [B][V][3] (the shape-basis kernel and sum order
+ * of ag_smplx_vertex_backward).  workspace: at least ag_smplx_shape_backward_workspace_floats(m, B) device floats. */
+size_t ag_smplx_shape_backward_workspace_floats(const AgSmplxModel* m, int32_t B);
+int ag_smplx_shape_backward(const AgSmplxModel* m, int32_t B, const float* dL_dv_shaped, float* dL_dshape_components, float* workspace,
+                            size_t workspace_floats, void* stream);
+
+/*
+ * ag_smplx_backward extended by what the vertex path hands over; each of the four may be NULL (absent):
+ *   dL_dA_skin [B][J][12]: added to dL_dA's rows 0-2 everywhere except in dL_dtransl (the skinning read the matrices before transl);
+ *   dL_dfeat [B][J-1][9]: a gradient on the local rotations R[1:] (lbs.py:221 pose_feature = R[1:] - I), added ahead of the Rodrigues
+ *   backward; dL_dtransl_add [B][3] and dL_dshape_components_add [B][NB]: added last to the two outputs of the same name.
+ * Outputs and everything else as ag_smplx_backward.  One wave per pose; deterministic.
+ */
+int ag_smplx_backward_full(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* dL_dA,
+                           const float* dL_djoints, const float* dL_dA_skin, const float* dL_dfeat, const float* dL_dtransl_add,
+                           const float* dL_dshape_components_add, float* dL_dfull_pose, float* dL_dtransl, float* dL_dshape_components,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
