@@ -152,6 +152,12 @@ class AgSmplxModel(ctypes.Structure):
         "v_template", "shapedirs", "posedirs", "J_regressor", "parents", "lbs_weights", "joint_template", "joint_dirs")]
 
 
+class AgMeshRasterArgs(ctypes.Structure):     # include/ag_subject_maps.h
+    _fields_ = ([(n, c_i32) for n in ("V", "F", "W", "H", "cull", "flip_rows", "mirror_cols", "out_col0", "out_stride", "reserved")]
+                + [("view", c_f * 12)] + [(n, c_vp) for n in ("vertices", "faces", "face_id", "bary", "workspace")]
+                + [("workspace_bytes", c_sz)])
+
+
 # every symbol include/*.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ag_abi_version", ctypes.c_int, []),
@@ -237,6 +243,13 @@ SYMBOLS = [
     ("ag_lbs_backward_joints_workspace_bytes", c_sz, [c_i32, c_i32]),
     ("ag_lbs_backward_joints", ctypes.c_int, [ctypes.POINTER(AgLbsArgs), c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     ("ag_hand_fuse", ctypes.c_int, [ctypes.POINTER(AgHandFuseArgs), c_vp]),
+    # include/ag_subject_maps.h
+    ("ag_mesh_rasterize_ortho_workspace_bytes", c_sz, [c_i32, c_i32]),
+    ("ag_mesh_rasterize_ortho", ctypes.c_int, [ctypes.POINTER(AgMeshRasterArgs), c_vp]),
+    ("ag_mesh_resolve_attribute_workspace_bytes", c_sz, [c_i32, c_i32, c_i32]),
+    ("ag_mesh_resolve_attribute", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    ("ag_knn_mean_dist2_workspace_bytes", c_sz, [c_i32, c_i32]),
+    ("ag_knn_mean_dist2", ctypes.c_int, [c_vp, c_i32, ctypes.POINTER(c_f), c_f, ctypes.POINTER(c_i32), c_vp, c_vp, c_vp, c_sz, c_vp]),
     # include/ag_styleunet.h
     ("ag_fused_bias_act", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_f, ctypes.c_int64, ctypes.c_int64, c_i32, c_vp]),
     ("ag_upfirdn2d", ctypes.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 13 + [c_vp]),

@@ -189,7 +189,9 @@ class AvatarNet(nn.Module):
     """
 
     def __init__(self, opt: Optional[dict] = None, *, cano_smpl_map: torch.Tensor, lbs: torch.Tensor,
-                 cano_nml_map: Optional[torch.Tensor] = None, device="cuda"):
+                 cano_nml_map: Optional[torch.Tensor] = None, device="cuda", log_scale: Optional[torch.Tensor] = None):
+        """``log_scale`` [N] (keyword-only): the canonical Gaussians' initial log scale, e.g. ``subject_maps.knn_log_scale`` of the
+        canonical points; ``None`` computes it on the host with scipy as before."""
         super().__init__()
         from .styleunet import DualStyleUNet
         opt = dict(opt or {})
@@ -206,7 +208,12 @@ class AvatarNet(nn.Module):
         N = init_points.shape[0]
         if lbs.shape[0] != N:
             raise ValueError(f"lbs has {lbs.shape[0]} rows, the canonical map has {N} valid pixels")
-        log_scale = torch.from_numpy(_knn3_log_scale(init_points.cpu().numpy()))
+        if log_scale is None:
+            log_scale = torch.from_numpy(_knn3_log_scale(init_points.cpu().numpy()))
+        elif tuple(log_scale.shape) != (N,):
+            raise ValueError(f"log_scale has shape {tuple(log_scale.shape)}, the canonical map has {N} valid pixels")
+        else:
+            log_scale = log_scale.detach().to(torch.float32)
         rot = torch.zeros(N, 4)
         rot[:, 0] = 1.0
         self.core = AvatarRenderCore(mask.to(dev), init_points.to(dev), torch.full((N, 1), float(np.log(0.1 / 0.9))).to(dev),
@@ -243,6 +250,46 @@ class AvatarNet(nn.Module):
         if (opt or {}).get('with_viewdirs', True):
             nml = torch.from_numpy(exr.imread(os.path.join(d, 'cano_smpl_nml_map.exr')))
         return cls(opt, cano_smpl_map=cano, lbs=lbs, cano_nml_map=nml, device=device)
+
+    @classmethod
+    def from_mesh(cls, opt: Optional[dict], vertices: torch.Tensor, faces: torch.Tensor, lbs_weights: torch.Tensor,
+                  normals: Optional[torch.Tensor] = None, size: int = 1024, device="cuda") -> "AvatarNet":
+        """From the subject's canonical mesh (vertices [V, 3], faces [F, 3], skinning weights [V, J], all on the GPU): what the
+        reference gets by running ``gen_data/gen_pos_maps.py`` first and reading its files (``subject_maps.canonical_maps``).  ``normals``
+        default to ``subject_maps.vertex_normals``.  The scale initialiser runs on the device k-NN.  The mesh must live on ``device``.
+
+        ``net.subject_maps`` keeps what ``subject_maps.write_subject_dir`` writes plus ``mask``, ``log_scale`` and ``cano_center``: the
+        two dense [S, 2S, 3] maps (50 MB at S = 1024) stay alive with the module; ``init_pts_lbs`` IS the core's ``lbs`` buffer, not a
+        copy; the face ids and barycentrics are dropped."""
+        from . import subject_maps as sm
+        dev = torch.device(device)
+        if not isinstance(vertices, torch.Tensor) or vertices.device.type != dev.type or (dev.index is not None and vertices.device.index != dev.index):
+            raise ValueError(f"from_mesh: the mesh must be on the module's device ({dev}); there is no host path")
+        if normals is None:
+            normals = sm.vertex_normals(vertices, faces)
+        maps = sm.canonical_maps(vertices, faces, normals, lbs_weights, size=size)
+        nml = maps["cano_smpl_nml_map"] if (opt or {}).get('with_viewdirs', True) else None
+        net = cls(opt, cano_smpl_map=maps["cano_smpl_pos_map"], lbs=maps["init_pts_lbs"], cano_nml_map=nml, device=device,
+                  log_scale=maps["log_scale"])
+        net.subject_maps = {k: maps[k] for k in ("cano_smpl_pos_map", "cano_smpl_nml_map", "init_pts_lbs", "log_scale", "mask", "cano_center")}
+        return net
+
+    @classmethod
+    def from_smplx(cls, opt: Optional[dict], smplx_model, betas: torch.Tensor, size: int = 1024, device="cuda") -> "AvatarNet":
+        """From a ``smplx.SMPLX`` model and the subject's ``betas`` [1, B]: the model's forward at the reference's canonical pose
+        (``config.py:9-15``: zero pose, the two hips rotated +-25 degrees about z) gives the vertices, the model its faces and skinning
+        weights (``gen_pos_maps.py:63-77,85,132``).  ``betas`` must be on the model's device, which must be ``device``."""
+        import math
+        dev = smplx_model.v_template.device
+        if not isinstance(betas, torch.Tensor) or betas.device != dev:
+            raise ValueError(f"from_smplx: betas must be a tensor on the model's device ({dev}); there is no host path")
+        body_pose = torch.zeros(1, 63, device=dev)
+        body_pose[0, 2], body_pose[0, 5] = math.radians(25), math.radians(-25)          # cano_smpl_pose[3 + 3*1 + 2], [3 + 3*2 + 2]
+        with torch.no_grad():
+            out = smplx_model(betas=betas.float(), global_orient=torch.zeros(1, 3, device=dev),
+                              transl=torch.zeros(1, 3, device=dev), body_pose=body_pose)
+        faces = torch.from_numpy(np.asarray(smplx_model.faces).astype(np.int32)).to(dev)
+        return cls.from_mesh(opt, out.vertices[0].contiguous(), faces, smplx_model.lbs_weights, size=size, device=device)
 
     @classmethod
     def synthetic(cls, opt: Optional[dict] = None, S: int = 1024, J: int = 55, seed: int = 31359, device="cuda") -> "AvatarNet":

@@ -107,6 +107,59 @@ def avatar_map_gaussians(S: int = 1024, seed: int = SEED) -> Dict[str, object]:
     }
 
 
+def _lattice_surface(radius, centre, n_lat: int, n_lon: int):
+    """Closed surface x = centre + radius(theta, phi) * direction on an n_lat x n_lon latitude / longitude lattice with two pole fans,
+    wound counter-clockwise seen from outside.  -> (vertices [n_lat * n_lon + 2, 3] float64, faces [2 * n_lon * n_lat, 3] int64)."""
+    theta = math.pi * (np.arange(n_lat) + 1.0) / (n_lat + 1.0)                # polar angle from +y, poles excluded
+    phi = 2.0 * math.pi * np.arange(n_lon) / n_lon
+    T, P = np.meshgrid(theta, phi, indexing="ij")
+    T = np.concatenate([T.reshape(-1), [0.0, math.pi]])
+    P = np.concatenate([P.reshape(-1), [0.0, 0.0]])
+    d = np.stack([np.sin(T) * np.cos(P), np.cos(T), np.sin(T) * np.sin(P)], 1)
+    v = np.asarray(centre, np.float64) + radius(T, P)[:, None] * d
+    i, j = np.meshgrid(np.arange(n_lat - 1), np.arange(n_lon), indexing="ij")
+    a, b = (i * n_lon + j).reshape(-1), (i * n_lon + (j + 1) % n_lon).reshape(-1)
+    c, e = a + n_lon, b + n_lon                                                # the ring below
+    jj = np.arange(n_lon)
+    north, south = n_lat * n_lon, n_lat * n_lon + 1
+    last = (n_lat - 1) * n_lon
+    faces = np.concatenate([np.stack([a, b, c], 1), np.stack([b, e, c], 1),
+                            np.stack([np.full(n_lon, north), (jj + 1) % n_lon, jj], 1),
+                            np.stack([np.full(n_lon, south), last + jj, last + (jj + 1) % n_lon], 1)], 0)
+    return v, faces.astype(np.int64)
+
+
+def body_mesh(J: int = 55, second_component: bool = True) -> Dict[str, np.ndarray]:
+    """A synthetic SURFACE of SMPL-X's size for the canonical-map path (``subject_maps.canonical_maps``): the random vertices and
+    faces of ``smplx_model_arrays`` are a triangle soup, a stress input and no surface.
+
+    First component: a closed, consistently wound (counter-clockwise from outside), star-shaped lobed surface -- an ellipsoid of
+    half-axes (0.5, 0.9, 0.2) m whose radius is modulated by smooth lobes -- on a 145 x 72 latitude / longitude lattice with two
+    pole fans: 10 442 vertices and 20 880 faces (SMPL-X: 10 475 and 20 908), inside the 2 m window of the canonical maps (1.19 x 1.8 m:
+    wide enough that a face still projects to about a pixel on a 256^2 map).
+    ``second_component``: a small closed sphere-like surface (110 vertices, 216 faces) that INTERSECTS the first, as the SMPL-X
+    eyeballs intersect the head.  ``lbs_weights`` [V, J]: 4-sparse rows that vary smoothly over the surface (cubic B-spline weights of
+    four consecutive joints along the body's long axis; rows sum to 1).  Deterministic, no random numbers."""
+    def lobed(T, P):
+        base = 1.0 / np.sqrt((np.sin(T) * np.cos(P) / 0.5) ** 2 + (np.cos(T) / 0.9) ** 2 + (np.sin(T) * np.sin(P) / 0.2) ** 2)
+        return base * (1.0 + 0.18 * np.sin(T) ** 2 * np.cos(4.0 * T) * np.cos(2.0 * P) + 0.10 * np.sin(T) ** 2 * np.sin(3.0 * P + 2.0 * T))
+
+    v, f = _lattice_surface(lobed, (0.013, -0.21, 0.017), 145, 72)
+    if second_component:
+        rim = v[(np.abs(v[:, 1] - (v[:, 1].max() - 0.12)).argmin())]         # a surface point near the top: the small sphere straddles it
+        v2, f2 = _lattice_surface(lambda T, P: 0.03 * (1.0 + 0.1 * np.cos(3.0 * P) * np.sin(T)), rim, 9, 12)
+        f = np.concatenate([f, f2 + v.shape[0]], 0)
+        v = np.concatenate([v, v2], 0)
+    y = v[:, 1]
+    s = (y - y.min()) / (y.max() - y.min()) * (J - 3) * (1.0 - 1e-9)          # joints k .. k+3, k = floor(s) in [0, J-4]
+    k = np.floor(s).astype(np.int64)
+    t = s - k
+    basis = np.stack([(1 - t) ** 3, 3 * t ** 3 - 6 * t ** 2 + 4, -3 * t ** 3 + 3 * t ** 2 + 3 * t + 1, t ** 3], 1) / 6.0
+    w = np.zeros((v.shape[0], J))
+    np.put_along_axis(w, k[:, None] + np.arange(4)[None], basis, 1)
+    return {"vertices": v.astype(f32), "faces": f.astype(np.int32), "lbs_weights": w.astype(f32)}
+
+
 def free_view_cameras(n_views: int = 8, img: int = 1024, focal: float = 1100.0, dist: float = 2.5) -> List[Dict[str, object]]:
     cams = []
     for i in range(n_views):
