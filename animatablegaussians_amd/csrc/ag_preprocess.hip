@@ -210,7 +210,8 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
                 // needs a positive definite conic; any other conic is never culled by it.
                 float r2 = 3.0e38f, qc = 3.0e38f;
                 if (lambda1 < 1.0e4f && lambda1 > 0.f && op >= 0.f) {
-                    const float lg = __logf(255.0f * op) + 0.01f;   // -inf for op == 0
+                    // op < 1/255 needs no slack: alpha = op * exp(power <= 0) rounds to at most op, below the blend's threshold at every pixel
+                    const float lg = (op < 1.0f / 255.0f) ? -1.0f : __logf(255.0f * op) + 0.01f;
                     r2 = (lg > 0.f) ? 2.0f * lambda1 * lg * 1.01f : -1.0f;
                     const bool pd = ca > 0.f && cc > 0.f && (ca * cc - cb * cb) > 0.f;
                     qc = (lg > 0.f) ? (pd ? 2.0f * lg * 1.01f : 3.0e38f) : -1.0f;

@@ -68,7 +68,42 @@ def build(name):
     print(f"{name}: R={st['num_rendered']} visible={int(vis.sum())} -> {os.path.getsize(path) / 1024:.0f} KiB")
 
 
+EDGE_INPUTS = ("means3D", "scales", "rotations", "opacities", "colors", "bg", "dL_dcolor", "dL_ddepth", "dL_dalpha")
+EDGE_DIGESTS = ("point_list", "ranges", "n_contrib", "color", "depth", "alpha")
+
+
+def build_edge_clamp_sm2():
+    """raster_edge_clamp_sm2.npz: the reference at ``scale_modifier = 2`` on tests/raster_edge_scenes.frustum_clamp_scene (an asymmetric
+    camera, a third of the drawn splats beyond the frustum clamp of computeCov2D).  The scene is seeded, so the fixture carries digests of the
+    inputs instead of the inputs; per-Gaussian state and every gradient in full, the sorted lists and the images as digests."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import helpers as h
+    import raster_edge_scenes as es
+    sc, cam, _, _ = es.frustum_clamp_scene(2.0)
+    W, H = cam["img_w"], cam["img_h"]
+    r = ref_raster.RefRasterizer()
+    st = r.forward(sc["means3D"], sc["colors"], sc["opacities"], sc["scales"], sc["rotations"], sc["bg"], cam["viewmatrix"],
+                   cam["projmatrix"], cam["campos"], cam["tanfovx"], cam["tanfovy"], W, H, scale_modifier=2.0)
+    g = r.backward(sc["dL_dcolor"], sc["dL_ddepth"], sc["dL_dalpha"])
+    out = {"scale_modifier": np.array([2.0]), "st_num_rendered": np.array([st["num_rendered"]], np.int64)}
+    for k in EDGE_INPUTS:
+        out["digest_in_" + k] = np.array(h.bits_digest(sc[k]))
+    vis = st["radii"] > 0
+    for k in ("radii", "tiles_touched"):
+        out["st_" + k] = st[k]
+    for k in ("depths", "means2D", "cov3D", "conic_opacity"):
+        out["st_" + k] = np.where(vis.reshape((-1,) + (1,) * (st[k].ndim - 1)), st[k], 0).astype(st[k].dtype)
+    for k in EDGE_DIGESTS:
+        out["digest_st_" + k] = np.array(h.bits_digest(st[k]))
+    for k, v in g.items():
+        out["g_" + k] = v
+    path = os.path.join(HERE, "raster_edge_clamp_sm2.npz")
+    np.savez_compressed(path, **out)
+    print(f"raster_edge_clamp_sm2: R={st['num_rendered']} visible={int(vis.sum())} -> {os.path.getsize(path) / 1024:.0f} KiB")
+
+
 if __name__ == "__main__":
     assert ref_raster.available(), "build oracle/_ref first: python oracle/ref_build.py"
     for n in SCENES:
         build(n)
+    build_edge_clamp_sm2()

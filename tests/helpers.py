@@ -11,28 +11,28 @@ def cam_of(scene_or_cam):
     return camera.camera_from_intr_extr(scene_or_cam["extr"], scene_or_cam["intr"], scene_or_cam["img_w"], scene_or_cam["img_h"])
 
 
-def oracle_forward(scene, cam, **kw):
+def oracle_forward(scene, cam, scale_modifier=1.0, **kw):
     from oracle import raster_oracle as ro
     return ro.forward(scene["means3D"], scene["colors"], scene["opacities"], scene.get("scales"), scene.get("rotations"),
                       scene["bg"], cam["viewmatrix"], cam["projmatrix"], cam["tanfovx"], cam["tanfovy"],
-                      cam["img_w"], cam["img_h"], cov3D_precomp=scene.get("cov3D_precomp"), **kw)
+                      cam["img_w"], cam["img_h"], scale_modifier=scale_modifier, cov3D_precomp=scene.get("cov3D_precomp"), **kw)
 
 
-def oracle_backward(st, scene, cam, grads):
+def oracle_backward(st, scene, cam, grads, scale_modifier=1.0):
     from oracle import raster_oracle as ro
     return ro.backward(st, scene["means3D"], scene["colors"], scene.get("scales"), scene.get("rotations"), scene["bg"],
                        cam["viewmatrix"], cam["projmatrix"], cam["tanfovx"], cam["tanfovy"],
-                       grads["dL_dcolor"], grads["dL_ddepth"], grads["dL_dalpha"],
+                       grads["dL_dcolor"], grads["dL_ddepth"], grads["dL_dalpha"], scale_modifier=scale_modifier,
                        cov3D_precomp=scene.get("cov3D_precomp"))
 
 
-def gpu_settings(scene, cam, device="cuda", debug=False):
+def gpu_settings(scene, cam, device="cuda", debug=False, scale_modifier=1.0):
     import torch
     from animatablegaussians_amd.rasterizer import GaussianRasterizationSettings
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
     return GaussianRasterizationSettings(
         image_height=cam["img_h"], image_width=cam["img_w"], tanfovx=cam["tanfovx"], tanfovy=cam["tanfovy"],
-        bg=t(scene["bg"]), scale_modifier=1.0, viewmatrix=t(cam["viewmatrix"]), projmatrix=t(cam["projmatrix"]),
+        bg=t(scene["bg"]), scale_modifier=scale_modifier, viewmatrix=t(cam["viewmatrix"]), projmatrix=t(cam["projmatrix"]),
         sh_degree=0, campos=t(cam["campos"]), prefiltered=False, debug=debug)
 
 
@@ -56,17 +56,17 @@ def _scratch_view(buf, off, nbytes, dtype):
     return buf[start:start + nbytes].cpu().numpy().view(dtype)
 
 
-def gpu_native_forward(scene, cam, device="cuda"):
+def gpu_native_forward(scene, cam, device="cuda", scale_modifier=1.0):
     """Call the `_C.rasterize_gaussians` equivalent and unpack the private scratch for comparison."""
     import torch
     from animatablegaussians_amd import _lib
     from animatablegaussians_amd.rasterizer import native_rasterize_gaussians
-    rs = gpu_settings(scene, cam, device)
+    rs = gpu_settings(scene, cam, device, scale_modifier=scale_modifier)
     inp = gpu_inputs(scene, device)
     empty = torch.Tensor([])
     e = lambda v: empty if v is None else v  # noqa: E731
     R, color, depth, alpha, radii, geom, binning, img = native_rasterize_gaussians(
-        rs.bg, inp["means3D"], inp["colors"], inp["opacities"], e(inp["scales"]), e(inp["rotations"]), 1.0,
+        rs.bg, inp["means3D"], inp["colors"], inp["opacities"], e(inp["scales"]), e(inp["rotations"]), scale_modifier,
         e(inp["cov3D_precomp"]), rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
         empty, 0, rs.campos, False, True)
     P, W, H = scene["means3D"].shape[0], cam["img_w"], cam["img_h"]
@@ -101,7 +101,7 @@ def gpu_native_forward(scene, cam, device="cuda"):
     return st
 
 
-def gpu_native_backward(fw, grads, alphas=None):
+def gpu_native_backward(fw, grads, alphas=None, scale_modifier=1.0):
     """`_C.rasterize_gaussians_backward` equivalent on the forward state `fw` (from gpu_native_forward).
     `alphas` overrides the saved forward alpha map (an explicit input of the reference's backward too).
     Returns the 8 API gradients plus the internal accumulators dL_dconic [P,4] and dL_ddepths [P,1]."""
@@ -118,7 +118,7 @@ def gpu_native_backward(fw, grads, alphas=None):
     al = t["alpha"] if alphas is None else torch.from_numpy(np.ascontiguousarray(alphas)).to(dev)
     g = lambda k: torch.from_numpy(np.ascontiguousarray(grads[k])).to(dev)  # noqa: E731
     out = native_rasterize_gaussians_backward(
-        rs.bg, inp["means3D"], t["radii"], inp["colors"], e(inp["scales"]), e(inp["rotations"]), 1.0,
+        rs.bg, inp["means3D"], t["radii"], inp["colors"], e(inp["scales"]), e(inp["rotations"]), scale_modifier,
         e(inp["cov3D_precomp"]), rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, g("dL_dcolor"), g("dL_ddepth"),
         g("dL_dalpha"), empty, 0, rs.campos, t["geom"], fw["num_rendered"], t["binning"], t["img"], al, True,
         _accum_buffer=accum)
@@ -131,6 +131,18 @@ def gpu_native_backward(fw, grads, alphas=None):
     res["dL_dconic"] = np.stack([nhop * acc[:, 2], nhop * acc[:, 3], np.zeros(P), nhop * acc[:, 4]], 1)
     res["dL_ddepths"] = acc[:, 9:10].copy()
     return res
+
+
+def _bitexact(gpu, ref):
+    for k in ("radii", "tiles_touched"):
+        assert np.array_equal(gpu[k], ref[k]), f"{k} not bit-exact: {(gpu[k] != ref[k]).sum()} differ"
+    vis = ref["radii"] > 0   # per-Gaussian state is only defined (and only consumed) for rasterized Gaussians
+    for k in ("means2D", "depths", "conic_opacity", "cov3D"):
+        a, b = gpu[k][vis].view(np.uint32), ref[k][vis].view(np.uint32)
+        assert np.array_equal(a, b), f"{k} not bit-exact: {(a != b).sum()} words differ, max abs {np.abs(gpu[k] - ref[k]).max()}"
+    assert gpu["num_rendered"] == ref["num_rendered"]
+    assert np.array_equal(gpu["ranges"], ref["ranges"]), "tile ranges differ"
+    assert np.array_equal(gpu["point_list"], ref["point_list"]), "sorted point_list differs"
 
 
 def assert_image_parity(gpu, ref, atol=1e-4, fragile_atol=6e-3, max_fragile_frac=5e-3):

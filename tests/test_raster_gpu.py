@@ -17,16 +17,7 @@ from animatablegaussians_amd import synth
 pytestmark = pytest.mark.gpu
 
 
-def _bitexact(gpu, ref):
-    for k in ("radii", "tiles_touched"):
-        assert np.array_equal(gpu[k], ref[k]), f"{k} not bit-exact: {(gpu[k] != ref[k]).sum()} differ"
-    vis = ref["radii"] > 0   # per-Gaussian state is only defined (and only consumed) for rasterized Gaussians
-    for k in ("means2D", "depths", "conic_opacity", "cov3D"):
-        a, b = gpu[k][vis].view(np.uint32), ref[k][vis].view(np.uint32)
-        assert np.array_equal(a, b), f"{k} not bit-exact: {(a != b).sum()} words differ, max abs {np.abs(gpu[k] - ref[k]).max()}"
-    assert gpu["num_rendered"] == ref["num_rendered"]
-    assert np.array_equal(gpu["ranges"], ref["ranges"]), "tile ranges differ"
-    assert np.array_equal(gpu["point_list"], ref["point_list"]), "sorted point_list differs"
+_bitexact = h._bitexact
 
 
 @pytest.mark.parametrize("P,img", [(10000, 512), (3000, 500)])
@@ -138,10 +129,10 @@ def test_tile_sort_every_size_class_is_bit_exact():
     _bitexact(gpu, ref)
 
 
-def _run_autograd(scene, cam, grads):
+def _run_autograd(scene, cam, grads, scale_modifier=1.0):
     import torch
     from animatablegaussians_amd.rasterizer import GaussianRasterizer
-    rs = h.gpu_settings(scene, cam)
+    rs = h.gpu_settings(scene, cam, scale_modifier=scale_modifier)
     inp = h.gpu_inputs(scene, requires_grad=True)
     means2D = torch.zeros_like(inp["means3D"], requires_grad=True)
     color, radii, depth, alpha = GaussianRasterizer(rs)(
