@@ -250,6 +250,10 @@ SYMBOLS = [
     ("ag_mesh_resolve_attribute", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
     ("ag_knn_mean_dist2_workspace_bytes", c_sz, [c_i32, c_i32]),
     ("ag_knn_mean_dist2", ctypes.c_int, [c_vp, c_i32, ctypes.POINTER(c_f), c_f, ctypes.POINTER(c_i32), c_vp, c_vp, c_vp, c_sz, c_vp]),
+    # include/ag_metrics.h
+    ("ag_psnr_ssim_workspace_bytes", c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    ("ag_psnr_ssim", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_double), c_i32, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     # include/ag_styleunet.h
     ("ag_fused_bias_act", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_f, ctypes.c_int64, ctypes.c_int64, c_i32, c_vp]),
     ("ag_upfirdn2d", ctypes.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 13 + [c_vp]),

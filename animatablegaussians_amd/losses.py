@@ -21,7 +21,14 @@ def mask_bbox(mask) -> tuple:
     computed there (``items['mask_bbox']``) spares the training step the device read-back the reference pays in every iteration."""
     import numpy as np
     m = np.asarray(mask) > 0
-    vs, us = np.nonzero(m.any(1))[0], np.nonzero(m.any(0))[0]
+    return bbox_from_profiles(m.any(1), m.any(0))
+
+
+def bbox_from_profiles(any_rows, any_cols) -> tuple:
+    """(min_v, min_u, max_v, max_u) from the HOST row and column profiles ``(mask > 0).any(1)``, ``.any(0)``: the arithmetic of
+    ``mask_bbox``, shared with ``metrics.eval_crop``, which reads back the two profiles of a device mask instead of the mask."""
+    import numpy as np
+    vs, us = np.nonzero(np.asarray(any_rows))[0], np.nonzero(np.asarray(any_cols))[0]
     return int(vs[0]), int(us[0]), int(vs[-1]), int(us[-1])
 
 
