@@ -254,6 +254,8 @@ SYMBOLS = [
     ("ag_psnr_ssim_workspace_bytes", c_sz, [c_i32, c_i32, c_i32, c_i32]),
     ("ag_psnr_ssim", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_double), c_i32, ctypes.c_double, ctypes.c_double,
                                     ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    # include/ag_weight_volume.h
+    ("ag_weight_volume_sample", ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, ctypes.c_int64, ctypes.POINTER(c_f), c_vp, c_vp]),
     # include/ag_styleunet.h
     ("ag_fused_bias_act", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_f, ctypes.c_int64, ctypes.c_int64, c_i32, c_vp]),
     ("ag_upfirdn2d", ctypes.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 13 + [c_vp]),

@@ -268,11 +268,44 @@ class AvatarNet(nn.Module):
         if normals is None:
             normals = sm.vertex_normals(vertices, faces)
         maps = sm.canonical_maps(vertices, faces, normals, lbs_weights, size=size)
+        return cls._from_canonical_maps(opt, maps, device)
+
+    @classmethod
+    def _from_canonical_maps(cls, opt, maps, device) -> "AvatarNet":
         nml = maps["cano_smpl_nml_map"] if (opt or {}).get('with_viewdirs', True) else None
         net = cls(opt, cano_smpl_map=maps["cano_smpl_pos_map"], lbs=maps["init_pts_lbs"], cano_nml_map=nml, device=device,
                   log_scale=maps["log_scale"])
         net.subject_maps = {k: maps[k] for k in ("cano_smpl_pos_map", "cano_smpl_nml_map", "init_pts_lbs", "log_scale", "mask", "cano_center")}
         return net
+
+    @classmethod
+    def from_template(cls, opt: Optional[dict], vertices: torch.Tensor, faces: torch.Tensor, weight_volume,
+                      normals: Optional[torch.Tensor] = None, size: int = 1024, device="cuda") -> "AvatarNet":
+        """From a clothed subject's canonical TEMPLATE mesh (vertices [V, 3], faces [F, 3], on the GPU) and its blend-weight volume (a
+        ``weight_volume.WeightVolume`` on the same GPU): the ``using_template`` branch of ``gen_data/gen_pos_maps.py`` (:79-82, :128-130).
+        The maps are rendered from the template about the volume's ``center`` (the SMPL-X body's: ``subject_maps.canonical_maps``) and
+        the per-point skinning weights are trilinear samples of the diffused volume.  ``normals`` default to
+        ``subject_maps.vertex_normals``.  ``net.subject_maps`` is filled as ``from_mesh`` fills it."""
+        from . import subject_maps as sm
+        dev = torch.device(device)
+        if not isinstance(vertices, torch.Tensor) or vertices.device.type != dev.type or (dev.index is not None and vertices.device.index != dev.index):
+            raise ValueError(f"from_template: the mesh must be on the module's device ({dev}); there is no host path")
+        if normals is None:
+            normals = sm.vertex_normals(vertices, faces)
+        maps = sm.canonical_maps(vertices, faces, normals, size=size, weight_volume=weight_volume)
+        return cls._from_canonical_maps(opt, maps, device)
+
+    @classmethod
+    def from_template_dir(cls, opt: Optional[dict], data_dir: str, size: int = 1024, device="cuda") -> "AvatarNet":
+        """From a directory that holds only ``template.ply`` and ``cano_weight_volume.npz`` (``gen_pos_maps.py:79-81,129``): the mesh
+        is read on the host (``obj_io.load_mesh_ply``; normals stored in the file are used, otherwise computed), everything else runs
+        on the device.  ``subject_maps.write_subject_dir(data_dir, net.subject_maps)`` then writes what ``from_data_dir`` reads."""
+        from .obj_io import load_mesh_ply
+        from .weight_volume import WeightVolume
+        v, f, n = load_mesh_ply(os.path.join(data_dir, 'template.ply'))
+        volume = WeightVolume.load(os.path.join(data_dir, 'cano_weight_volume.npz'), device)
+        t = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+        return cls.from_template(opt, t(v), t(f), volume, normals=None if n is None else t(n), size=size, device=device)
 
     @classmethod
     def from_smplx(cls, opt: Optional[dict], smplx_model, betas: torch.Tensor, size: int = 1024, device="cuda") -> "AvatarNet":

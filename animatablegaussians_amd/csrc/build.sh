@@ -19,7 +19,7 @@ FAST="-ffp-contract=fast"
 compile() { # src flags
   local src="$1"; shift
   local obj="$OBJ/$(basename "${src%.hip}").o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/ag_common.h" -nt "$obj" ] || [ "$HERE/../../include/ag_raster.h" -nt "$obj" ] || [ "$HERE/../../include/ag_avatar.h" -nt "$obj" ] || [ "$HERE/../../include/ag_styleunet.h" -nt "$obj" ] || [ "$HERE/../../include/ag_conv.h" -nt "$obj" ] || [ "$HERE/../../include/ag_lpips.h" -nt "$obj" ] || [ "$HERE/../../include/ag_smplx.h" -nt "$obj" ] || [ "$HERE/ag_sh.h" -nt "$obj" ] || [ "$HERE/../../include/ag_layers.h" -nt "$obj" ] || [ "$HERE/../../include/ag_optim.h" -nt "$obj" ] || [ "$HERE/../../include/ag_linear.h" -nt "$obj" ] || [ "$HERE/../../include/ag_subject_maps.h" -nt "$obj" ] || [ "$HERE/../../include/ag_metrics.h" -nt "$obj" ]; then
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/ag_common.h" -nt "$obj" ] || [ "$HERE/../../include/ag_raster.h" -nt "$obj" ] || [ "$HERE/../../include/ag_avatar.h" -nt "$obj" ] || [ "$HERE/../../include/ag_styleunet.h" -nt "$obj" ] || [ "$HERE/../../include/ag_conv.h" -nt "$obj" ] || [ "$HERE/../../include/ag_lpips.h" -nt "$obj" ] || [ "$HERE/../../include/ag_smplx.h" -nt "$obj" ] || [ "$HERE/ag_sh.h" -nt "$obj" ] || [ "$HERE/../../include/ag_layers.h" -nt "$obj" ] || [ "$HERE/../../include/ag_optim.h" -nt "$obj" ] || [ "$HERE/../../include/ag_linear.h" -nt "$obj" ] || [ "$HERE/../../include/ag_subject_maps.h" -nt "$obj" ] || [ "$HERE/../../include/ag_metrics.h" -nt "$obj" ] || [ "$HERE/../../include/ag_weight_volume.h" -nt "$obj" ]; then
     echo "hipcc $(basename "$src") $*"
     rm -f "$obj"
     local log; log="$(mktemp)"
@@ -47,6 +47,8 @@ compile "$HERE/ag_linear.hip" $FAST &
 compile "$HERE/ag_subject_maps.hip" $EXACT &
 # fp64 window sums (include/ag_metrics.h): contraction changes nothing the contract states
 compile "$HERE/ag_metrics.hip" $FAST &
+# the trilinear weights and the eight-corner sum are stated op by op in include/ag_weight_volume.h
+compile "$HERE/ag_weight_volume.hip" $EXACT &
 fail=0
 for job in $(jobs -p); do wait "$job" || fail=1; done
 if [ "$fail" -ne 0 ]; then echo "build.sh: compilation failed" >&2; exit 1; fi

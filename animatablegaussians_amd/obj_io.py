@@ -71,3 +71,146 @@ def load_gaussians_from_ply(path: str, device="cuda") -> dict:
         'rotations': torch.nn.functional.normalize(t(rots)),
         'features_extr': t(extra),
     }
+
+
+# ---- triangle-mesh PLY (a subject's template.ply) -------------------------------------------------------------------------------
+# gen_pos_maps.py:81 reads the template with trimesh.load(process=False); trimesh is not in this image, so its reader is unpinned.
+# What follows is the format's own definition (Turk, "The PLY Polygon File Format"): a header of element / property lines, then the
+# elements in header order, ascii or binary in either byte order.
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def _ply_header(buf: bytes, path: str):
+    if buf[:3] != b'ply':
+        raise ValueError(f"{path}: not a PLY file")
+    end = buf.find(b'end_header')
+    nl = buf.find(b'\n', end)
+    if end < 0 or nl < 0:
+        raise ValueError(f"{path}: truncated PLY header")
+    fmt, elements = None, []                                   # elements: [name, count, [(property name, type) | (name, count type, item type)]]
+    for ln in buf[:end].decode('ascii', 'replace').splitlines()[1:]:
+        tok = ln.split()
+        if not tok or tok[0] in ('comment', 'obj_info'):
+            continue
+        if tok[0] == 'format':
+            fmt = tok[1]
+        elif tok[0] == 'element':
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == 'property' and elements:
+            types = tok[2:4] if tok[1] == 'list' else tok[1:2]
+            if any(t not in _PLY_TYPES for t in types):
+                raise ValueError(f"{path}: unknown property type in '{ln}'")
+            elements[-1][2].append((tok[4], tok[2], tok[3]) if tok[1] == 'list' else (tok[2], tok[1]))
+    if fmt not in ('ascii', 'binary_little_endian', 'binary_big_endian'):
+        raise ValueError(f"{path}: unknown PLY format {fmt}")
+    return fmt, elements, nl + 1
+
+
+def load_mesh_ply(path: str):
+    """-> (vertices float32 [V, 3], faces int32 [F, 3], normals float32 [V, 3] or None) of a triangle-mesh PLY: ``ascii``,
+    ``binary_little_endian`` or ``binary_big_endian``; vertex properties of any scalar type in any order (``x y z``, optional
+    ``nx ny nz``; others are skipped); faces in a list property ``vertex_indices`` or ``vertex_index`` with any integer count and
+    index types.  A face that is not a triangle and a file shorter than its header promises raise ``ValueError``.  Host numpy only."""
+    with open(path, 'rb') as f:
+        buf = f.read()
+    fmt, elements, pos = _ply_header(buf, path)
+    order = {'binary_little_endian': '<', 'binary_big_endian': '>'}.get(fmt)
+    tokens = buf[pos:].split() if fmt == 'ascii' else None
+    tpos = 0
+    vertex = faces = None
+    for name, count, props in elements:
+        scalar = all(len(p) == 2 for p in props)
+        is_faces = name == 'face'
+        if scalar:
+            if order is None:
+                if tpos + count * len(props) > len(tokens):
+                    raise ValueError(f"{path}: truncated PLY body (element {name})")
+                try:
+                    table = np.array(tokens[tpos:tpos + count * len(props)], dtype=np.float64).reshape(count, len(props))
+                except ValueError as e:
+                    raise ValueError(f"{path}: malformed ascii PLY body (element {name})") from e
+                tpos += count * len(props)
+                cols = {p[0]: table[:, i] for i, p in enumerate(props)}
+            else:
+                dt = np.dtype([(p[0], order + _PLY_TYPES[p[1]]) for p in props])
+                if pos + count * dt.itemsize > len(buf):
+                    raise ValueError(f"{path}: truncated PLY body (element {name})")
+                table = np.frombuffer(buf, dt, count, pos)
+                pos += count * dt.itemsize
+                cols = {p[0]: table[p[0]] for p in props}
+            if name == 'vertex':
+                vertex = cols
+            continue
+        # an element with list properties: rows of varying length, walked one by one (faces of a 21 k-face template: milliseconds)
+        rows = []
+        for _ in range(count):
+            for p in props:
+                if len(p) == 2:
+                    if order is None:
+                        if tpos + 1 > len(tokens):
+                            raise ValueError(f"{path}: truncated PLY body (element {name})")
+                        tpos += 1
+                    else:
+                        pos += np.dtype(_PLY_TYPES[p[1]]).itemsize
+                    continue
+                if order is None:
+                    if tpos + 1 > len(tokens):
+                        raise ValueError(f"{path}: truncated PLY body (element {name})")
+                    k = int(tokens[tpos])
+                    if tpos + 1 + k > len(tokens):
+                        raise ValueError(f"{path}: truncated PLY body (element {name})")
+                    items = [int(t) for t in tokens[tpos + 1:tpos + 1 + k]]
+                    tpos += 1 + k
+                else:
+                    ct, it = np.dtype(order + _PLY_TYPES[p[1]]), np.dtype(order + _PLY_TYPES[p[2]])
+                    if pos + ct.itemsize > len(buf):
+                        raise ValueError(f"{path}: truncated PLY body (element {name})")
+                    k = int(np.frombuffer(buf, ct, 1, pos)[0])
+                    pos += ct.itemsize
+                    if k < 0 or pos + k * it.itemsize > len(buf):
+                        raise ValueError(f"{path}: truncated PLY body (element {name})")
+                    items = np.frombuffer(buf, it, k, pos)
+                    pos += k * it.itemsize
+                if is_faces and p[0] in ('vertex_indices', 'vertex_index'):
+                    if k != 3:
+                        raise ValueError(f"{path}: face {len(rows)} has {k} vertices; only triangle meshes are read")
+                    rows.append(items)
+            if order is not None and pos > len(buf):
+                raise ValueError(f"{path}: truncated PLY body (element {name})")
+        if is_faces:
+            faces = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    if vertex is None or not all(k in vertex for k in 'xyz'):
+        raise ValueError(f"{path}: no vertex element with x, y, z")
+    v = np.stack([vertex[k] for k in 'xyz'], 1).astype(np.float32)
+    n = np.stack([vertex[k] for k in ('nx', 'ny', 'nz')], 1).astype(np.float32) if all(k in vertex for k in ('nx', 'ny', 'nz')) else None
+    if faces is None:
+        faces = np.zeros((0, 3), np.int64)
+    if faces.size and (faces.min() < 0 or faces.max() >= len(v)):
+        raise ValueError(f"{path}: a face index lies outside [0, {len(v)})")
+    return v, faces.astype(np.int32), n
+
+
+def save_mesh_ply(path: str, vertices, faces, normals=None) -> None:
+    """Write a triangle mesh as binary little-endian PLY: ``float x y z`` (+ ``nx ny nz``), ``list uchar int vertex_indices``."""
+    v = np.asarray(vertices, dtype='<f4').reshape(-1, 3)
+    f = np.asarray(faces).reshape(-1, 3)
+    names = ['x', 'y', 'z']
+    if normals is not None:
+        nm = np.asarray(normals, dtype='<f4').reshape(-1, 3)
+        if nm.shape != v.shape:
+            raise ValueError("normals must have one row per vertex")
+        v = np.concatenate([v, nm], 1)
+        names += ['nx', 'ny', 'nz']
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(v) + "".join(f"property float {k}\n" for k in names)
+              + "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(f))
+    rec = np.zeros(len(f), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+    rec['n'] = 3
+    rec['i'] = f
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, 'wb') as fh:
+        fh.write(header.encode('ascii'))
+        fh.write(np.ascontiguousarray(v).tobytes())
+        fh.write(rec.tobytes())

@@ -189,9 +189,15 @@ def knn_log_scale(points: torch.Tensor) -> torch.Tensor:
     return torch.log(torch.sqrt(torch.clamp_min(knn_dist2(points)[0], 1e-7)))
 
 
-def canonical_maps(vertices: torch.Tensor, faces: torch.Tensor, normals: torch.Tensor, lbs_weights: torch.Tensor,
-                   size: int = 1024) -> Dict[str, torch.Tensor]:
-    """The canonical part of ``gen_pos_maps.py`` (:75, :93-134, SMPL-X-as-template branch) plus the scale initialiser:
+def canonical_maps(vertices: torch.Tensor, faces: torch.Tensor, normals: torch.Tensor, lbs_weights: Optional[torch.Tensor] = None,
+                   size: int = 1024, *, weight_volume=None, center: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The canonical part of ``gen_pos_maps.py`` (:75, :93-134) plus the scale initialiser.  Without the keywords: the
+    SMPL-X-as-template branch, the mesh IS the body and ``lbs_weights`` [V, J] are interpolated.  With ``weight_volume`` (a
+    ``weight_volume.WeightVolume``): the ``using_template`` branch (:79-82, :128-130), the mesh is the clothed template,
+    ``lbs_weights`` may be ``None`` and ``init_pts_lbs = weight_volume.forward_weight(cano_pos_map[mask])``, not renormalised, as in
+    the reference.  ``center`` [3] (on the GPU) is the centre of the two views; default: the centre of the mesh's bounding box, or with
+    a volume its ``center`` -- the reference takes the centre of the SMPL-X body also when it renders a template (:75 runs before
+    :88), and that is the ``center`` ``gen_weight_volume.py:139`` stores.  Returns
 
     ``cano_smpl_pos_map`` / ``cano_smpl_nml_map`` [S, 2S, 3] (front | back, zeros where empty), ``mask`` [S, 2S] (``|pos| > 0``),
     ``init_pts_lbs`` [N, J] in ``map[mask]`` order -- interpolated with the RENDERED face and its barycentrics, where the reference
@@ -199,11 +205,18 @@ def canonical_maps(vertices: torch.Tensor, faces: torch.Tensor, normals: torch.T
     v = _dev(vertices, "vertices", torch.float32, 3)
     f = _dev(faces, "faces", torch.int32, 3)
     n = _dev(normals, "normals", torch.float32, 3)
-    w = _dev(lbs_weights, "lbs_weights", torch.float32)
-    if n.shape[0] != v.shape[0] or w.dim() != 2 or w.shape[0] != v.shape[0]:
+    if weight_volume is None or lbs_weights is not None:
+        w = _dev(lbs_weights, "lbs_weights", torch.float32)
+        if w.dim() != 2 or w.shape[0] != v.shape[0]:
+            raise ValueError("normals [V, 3] and lbs_weights [V, J] must have one row per vertex")
+    if n.shape[0] != v.shape[0]:
         raise ValueError("normals [V, 3] and lbs_weights [V, J] must have one row per vertex")
     S = int(size)
-    center = 0.5 * (v.amin(0) + v.amax(0))                                     # gen_pos_maps.py:75
+    if center is None:
+        center = 0.5 * (v.amin(0) + v.amax(0)) if weight_volume is None else weight_volume.center       # gen_pos_maps.py:75
+    center = _dev(center, "center", torch.float32).reshape(-1)
+    if center.numel() != 3:
+        raise ValueError(f"center must have 3 components, got {tuple(center.shape)}")
     front, back = view_matrices(center.cpu().numpy())
     face_id = torch.empty(S, 2 * S, dtype=torch.int32, device=v.device)
     bary = torch.empty(S, 2 * S, 3, dtype=torch.float32, device=v.device)
@@ -213,8 +226,11 @@ def canonical_maps(vertices: torch.Tensor, faces: torch.Tensor, normals: torch.T
     nml = resolve(face_id, bary, f, n)
     mask = torch.linalg.norm(pos, dim=-1) > 0.                                 # :126
     pix = mask_to_pix(mask)
-    lbs = resolve(face_id, bary, f, w, pix=pix)
     init_points = pos.reshape(-1, 3)[pix.long()]
+    if weight_volume is not None:
+        lbs = weight_volume.forward_weight(init_points)                         # :129-130
+    else:
+        lbs = resolve(face_id, bary, f, w, pix=pix)
     return {"cano_smpl_pos_map": pos, "cano_smpl_nml_map": nml, "mask": mask, "init_pts_lbs": lbs,
             "log_scale": knn_log_scale(init_points), "cano_center": center, "face_id": face_id, "bary": bary}
 

@@ -269,3 +269,41 @@ def smplx_pose_params(seed: int = SEED, n: int = 1) -> Dict[str, np.ndarray]:
         'left_hand_pose': (rng.standard_normal((n, 45)) * 0.3).astype(f32),
         'right_hand_pose': (rng.standard_normal((n, 45)) * 0.3).astype(f32),
     }
+
+
+def weight_volume_arrays(mesh: Dict[str, np.ndarray], res=(32, 32, 32), J: int = 55) -> Dict[str, np.ndarray]:
+    """A synthetic ``cano_weight_volume.npz`` around ``mesh`` (the stand-in for the SMPL-X body; ``body_mesh()``), with the array names,
+    shapes and dtypes ``gen_data/gen_weight_volume.py:164-170`` writes and its bounds rule (:136-150): a cube of 1.1 x the body's
+    longest extent about the centre of its bounding box.  The reference's volumes come out of a Poisson solver and libigl, neither of
+    which is available here; these are smooth analytic stand-ins with the same post-processing (:131-132: clipped to [0, 1], rows
+    normalised to sum 1): ``diff_weight_volume`` [X, Y, Z, J] from Gaussians of 12 cm about J centres along the body's long axis
+    over a floor of 1e-3 (every joint non-zero everywhere, as in a diffused volume: the dense skinning path), ``ori_weight_volume``
+    from sharper ones (4 cm) without a floor (far joints underflow to exact zeros), ``sdf_volume``
+    [X, Y, Z], positive inside, of the bounding ellipsoid.  Deterministic, no random numbers."""
+    v = np.asarray(mesh["vertices"], f32)
+    min_xyz, max_xyz = v.min(0).astype(f32), v.max(0).astype(f32)
+    max_len = f32(1.1) * (max_xyz - min_xyz).max()
+    center = (f32(0.5) * (min_xyz + max_xyz)).astype(f32)
+    bounds = np.stack([center - f32(0.5) * max_len, center + f32(0.5) * max_len], 0).astype(f32)
+    smpl_min, smpl_max = min_xyz.copy(), max_xyz.copy()
+    smpl_min[:2] -= 0.05
+    smpl_max[:2] += 0.05
+    smpl_min[2] -= 0.15
+    smpl_max[2] += 0.15
+    X, Y, Z = (int(r) for r in res)
+    axes = [np.linspace(bounds[0, d], bounds[1, d], r, dtype=np.float64) for d, r in enumerate((X, Y, Z))]
+    gx, gy, gz = np.meshgrid(*axes, indexing="ij")
+    cy = np.linspace(min_xyz[1], max_xyz[1], J, dtype=np.float64)
+    cx = center[0] + 0.25 * (max_xyz[0] - min_xyz[0]) * np.sin(np.arange(J) * 2.4)      # off the axis: the weights vary along x and z too
+    cz = center[2] + 0.25 * (max_xyz[2] - min_xyz[2]) * np.cos(np.arange(J) * 1.7)
+    d2 = (gx[..., None] - cx) ** 2 + (gy[..., None] - cy) ** 2 + (gz[..., None] - cz) ** 2
+
+    def weights(sigma, floor):
+        g = np.exp(-(d2 - d2.min(-1, keepdims=True)) / (2.0 * sigma * sigma)) + floor   # the nearest centre has weight 1 before normalising
+        g = np.clip(g, 0.0, 1.0)
+        return (g / g.sum(-1, keepdims=True)).astype(f32)
+
+    half = 0.5 * (max_xyz - min_xyz).astype(np.float64)
+    r = np.sqrt(((gx - center[0]) / half[0]) ** 2 + ((gy - center[1]) / half[1]) ** 2 + ((gz - center[2]) / half[2]) ** 2)
+    return {"diff_weight_volume": weights(0.12, 1e-3), "ori_weight_volume": weights(0.04, 0.0), "sdf_volume": ((1.0 - r) * half.min()).astype(f32),
+            "volume_bounds": bounds, "center": center, "smpl_bounds": np.stack([smpl_min, smpl_max], 0).astype(f32)}
