@@ -256,6 +256,8 @@ SYMBOLS = [
                                     ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     # include/ag_weight_volume.h
     ("ag_weight_volume_sample", ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, ctypes.c_int64, ctypes.POINTER(c_f), c_vp, c_vp]),
+    # include/ag_targets.h
+    ("ag_prepare_targets", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_styleunet.h
     ("ag_fused_bias_act", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_f, ctypes.c_int64, ctypes.c_int64, c_i32, c_vp]),
     ("ag_upfirdn2d", ctypes.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 13 + [c_vp]),
