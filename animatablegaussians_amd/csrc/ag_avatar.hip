@@ -8,6 +8,7 @@
 //   lbs fwd/bwd: the [N, J] blend-weight rows (220 B / Gaussian at J = 55, the dominant stream) are staged through
 //                wave-private LDS with fully coalesced loads and read back conflict-free (row stride J is odd);
 //                the J joint matrices are wave-uniform and come in through scalar loads.
+#include <atomic>
 #include "ag_common.h"
 #include "../../include/ag_avatar.h"
 
@@ -415,10 +416,15 @@ __device__ __forceinline__ void lbs_backward_gaussian(const AgLbsArgs& a, int n,
 }
 
 // Joint-matrix gradient, pass 1 (the blend and the rotation chain of lbs_backward_kernel again, plus the reduction of its workgroup): every workgroup writes its
-// slab [J][12] = sum over its 256 Gaussians of w_nj GM_n.  LDS: [4 waves][64][J] weight rows | [4][64][12] GM rows | [4][J][12] wave partials.
+// slab [J][12] = sum over its 256 Gaussians of w_nj GM_n.  LDS: [4 waves][64][J] weight rows | [4][64][12] GM rows; the [J][12] partial of a wave goes over its
+// own weight rows once every lane has read its columns (12 J <= 64 J floats), which is what lets J = 140 fit: (256 J + 3072) * 4 B = 155648 B of the 163840.
 // The sparse form is expanded into the dense row layout (zeros, then its K weights), so both forms run the same summation over the same
-// values in the same order: a skipped term is + 0 * GM, and the slabs are bit-identical.  Lane j of a wave sums its 64 rows in order;
-// the four wave partials are added in wave order.  No float atomics: the slabs are combined by lbs_joint_slab_reduce_kernel.
+// values in the same order: a skipped term is + 0 * GM, and the slabs are bit-identical.  Lane l of a wave sums columns l, l + 64, l + 128 over the 64 rows in
+// order, into registers; the four wave partials are added in wave order.  No float atomics: the slabs are combined by lbs_joint_slab_reduce_kernel.
+constexpr int kJointGradMaxJ = 140;                          // include/ag_avatar.h
+constexpr int kJointCols = (kJointGradMaxJ + 63) / 64;       // columns of the weight rows per lane: the kernel covers J <= 64 * kJointCols and
+                                                             // relies on ag_lbs_backward_joints refusing J > kJointGradMaxJ
+static_assert(kJointGradMaxJ <= 64 * kJointCols && (256 * kJointGradMaxJ + 3072) * 4 <= 160 * 1024, "the joint-gradient pass at its largest J");
 template <bool SPARSE>
 __global__ void __launch_bounds__(256) lbs_backward_joints_kernel(AgLbsArgs a, float* __restrict__ slabs)
 {
@@ -429,7 +435,6 @@ __global__ void __launch_bounds__(256) lbs_backward_joints_kernel(AgLbsArgs a, f
     const int rows = max(0, min(64, a.N - first));            // wave-uniform; 0 for the idle waves of the last workgroup
     float* tile = lds + (size_t)wave * 64 * J;
     float* gm_rows = lds + (size_t)4 * 64 * J + wave * 64 * 12;
-    float* part = lds + (size_t)4 * 64 * J + 4 * 64 * 12 + (size_t)wave * J * 12;
     const int n = first + lane;
     float GM[12];
 #pragma unroll
@@ -456,24 +461,36 @@ __global__ void __launch_bounds__(256) lbs_backward_joints_kernel(AgLbsArgs a, f
 #pragma unroll
     for (int k = 0; k < 12; k++) gm_rows[lane * 12 + k] = GM[k];
     __builtin_amdgcn_wave_barrier();
-    for (int j = lane; j < J; j += 64) {
-        float acc[12];
+    float acc[kJointCols][12];
 #pragma unroll
-        for (int k = 0; k < 12; k++) acc[k] = 0.f;
-        for (int r = 0; r < rows; r++) {
-            const float w = tile[r * J + j];
-            const float* g = gm_rows + r * 12;              // wave-uniform address: broadcast
+    for (int t = 0; t < kJointCols; t++) {
+        const int j = lane + 64 * t;
 #pragma unroll
-            for (int k = 0; k < 12; k++) acc[k] = fmaf(w, g[k], acc[k]);
+        for (int k = 0; k < 12; k++) acc[t][k] = 0.f;
+        if (j < J) {
+            for (int r = 0; r < rows; r++) {
+                const float w = tile[r * J + j];
+                const float* g = gm_rows + r * 12;              // wave-uniform address: broadcast
+#pragma unroll
+                for (int k = 0; k < 12; k++) acc[t][k] = fmaf(w, g[k], acc[t][k]);
+            }
         }
+    }
+    __builtin_amdgcn_wave_barrier();                        // every lane of the wave has read its columns: the partial may overwrite the rows
+    float* part = tile;                                     // [J][12]
 #pragma unroll
-        for (int k = 0; k < 12; k++) part[j * 12 + k] = acc[k];
+    for (int t = 0; t < kJointCols; t++) {
+        const int j = lane + 64 * t;
+        if (j < J) {
+#pragma unroll
+            for (int k = 0; k < 12; k++) part[j * 12 + k] = acc[t][k];
+        }
     }
     __syncthreads();
-    const float* p0 = lds + (size_t)4 * 64 * J + 4 * 64 * 12;
     const int JK = J * 12;
+    const size_t wave_stride = (size_t)64 * J;              // between the partials of two waves
     float* out = slabs + (size_t)blockIdx.x * JK;
-    for (int i = threadIdx.x; i < JK; i += 256) out[i] = ((p0[i] + p0[JK + i]) + p0[2 * JK + i]) + p0[3 * JK + i];
+    for (int i = threadIdx.x; i < JK; i += 256) out[i] = ((lds[i] + lds[wave_stride + i]) + lds[2 * wave_stride + i]) + lds[3 * wave_stride + i];
 }
 
 // Joint-matrix gradient, pass 2: dL/dA [J][4][4] = the sum of the slabs, in a fixed order.  A workgroup owns 16 of the J * 12 outputs:
@@ -587,9 +604,40 @@ int ag_gather_activate_backward(const AgGatherArgs* a, float* g_pos_map, float* 
     return check_hip(hipGetLastError(), "gather_backward_kernel");
 }
 
+// The dense kernels stage the 4 x 64 weight rows of a workgroup in LDS: 4 * 64 * J floats, which has to fit the device's LDS per workgroup
+// (163840 B on gfx950: J <= 160).  The sparse kernels use no LDS and take every J a uint8 index reaches.
+static int lbs_dense_lds_bytes(int J) { return 4 * 64 * J * (int)sizeof(float); }
+
+// LDS per workgroup of the current device (hipDeviceAttributeMaxSharedMemoryPerBlock), asked once per device.
+static int device_lds_bytes(int* bytes)
+{
+    constexpr int kDevices = 64;
+    static std::atomic<int> cached[kDevices];
+    int dev = 0, rc;
+    if ((rc = check_hip(hipGetDevice(&dev), "hipGetDevice"))) return rc;
+    const bool slot = dev >= 0 && dev < kDevices;
+    int v = slot ? cached[dev].load(std::memory_order_relaxed) : 0;
+    if (v <= 0) {
+        if ((rc = check_hip(hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev), "hipDeviceGetAttribute"))) return rc;
+        if (slot) cached[dev].store(v, std::memory_order_relaxed);
+    }
+    *bytes = v;
+    return AG_OK;
+}
+
 static int check_lbs(const AgLbsArgs* a)
 {
-    if (!a || a->N < 0 || a->J < 1 || a->J > kMaxJ) { set_error("bad lbs sizes (1 <= J <= %d)", kMaxJ); return AG_ERR_INVALID_ARGUMENT; }
+    if (!a || a->N < 0 || a->J < 1) { set_error("bad lbs sizes (N >= 0, J >= 1)"); return AG_ERR_INVALID_ARGUMENT; }
+    if (a->K <= 0) {            // dense: refuse here what the launch would refuse (also at N == 0: the contract does not depend on N)
+        int lds_max = 0, rc;
+        if ((rc = device_lds_bytes(&lds_max))) return rc;
+        if (a->J > lds_max / lbs_dense_lds_bytes(1)) {
+            set_error("dense lbs: J = %d stages %lld B of LDS per workgroup, the device has %d B (largest dense J = %d; the sparse form, K > 0, takes J <= %d)",
+                      a->J, (long long)a->J * lbs_dense_lds_bytes(1), lds_max, lds_max / lbs_dense_lds_bytes(1), kMaxJ);
+            return AG_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (a->J > kMaxJ) { set_error("bad lbs sizes (sparse rows: 1 <= J <= %d)", kMaxJ); return AG_ERR_INVALID_ARGUMENT; }
     if (a->N == 0) return AG_OK;
     const bool sparse = a->K > 0;
     if ((sparse ? (!a->sp_idx || !a->sp_w || a->K > a->J) : !a->lbs) || !a->jnt_mats || !a->positions || !a->rotations || !a->out_positions ||
@@ -600,11 +648,11 @@ static int check_lbs(const AgLbsArgs* a)
     return AG_OK;
 }
 
-static int lbs_lds_bytes(int J, const void* fn)
+// Dynamic LDS above 48 KiB has to be asked for per kernel; a refusal is this call's error, not the launch's.
+static int allow_lds(const void* fn, int bytes, const char* what)
 {
-    const int bytes = 4 * 64 * J * (int)sizeof(float);
-    if (bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return bytes;
+    if (bytes <= 48 * 1024) return AG_OK;
+    return check_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), what);
 }
 
 int ag_lbs_forward(const AgLbsArgs* a, void* stream)
@@ -615,7 +663,8 @@ int ag_lbs_forward(const AgLbsArgs* a, void* stream)
     if (a->K > 0) {
         hipLaunchKernelGGL(lbs_forward_kernel<true>, dim3((a->N + 255) / 256), dim3(256), 0, s, *a);
     } else {
-        const int lds = lbs_lds_bytes(a->J, reinterpret_cast<const void*>(&lbs_forward_kernel<false>));
+        const int lds = lbs_dense_lds_bytes(a->J);
+        if ((rc = allow_lds(reinterpret_cast<const void*>(&lbs_forward_kernel<false>), lds, "lbs_forward_kernel (LDS size)"))) return rc;
         hipLaunchKernelGGL(lbs_forward_kernel<false>, dim3((a->N + 255) / 256), dim3(256), lds, s, *a);
     }
     return check_hip(hipGetLastError(), "lbs_forward_kernel");
@@ -630,7 +679,8 @@ int ag_lbs_backward(const AgLbsArgs* a, float* g_positions, float* g_rotations, 
     if (a->K > 0) {
         hipLaunchKernelGGL(lbs_backward_kernel<true>, dim3((a->N + 255) / 256), dim3(256), 0, s, *a, g_positions, g_rotations);
     } else {
-        const int lds = lbs_lds_bytes(a->J, reinterpret_cast<const void*>(&lbs_backward_kernel<false>));
+        const int lds = lbs_dense_lds_bytes(a->J);
+        if ((rc = allow_lds(reinterpret_cast<const void*>(&lbs_backward_kernel<false>), lds, "lbs_backward_kernel (LDS size)"))) return rc;
         hipLaunchKernelGGL(lbs_backward_kernel<false>, dim3((a->N + 255) / 256), dim3(256), lds, s, *a, g_positions, g_rotations);
     }
     return check_hip(hipGetLastError(), "lbs_backward_kernel");
@@ -655,20 +705,18 @@ int ag_lbs_backward_joints(const AgLbsArgs* a, float* g_positions, float* g_rota
         return AG_ERR_SCRATCH_TOO_SMALL;
     }
     const int nslab = (a->N + 255) / 256;
-    const int lds = (4 * 64 * a->J + 4 * 64 * 12 + 4 * a->J * 12) * (int)sizeof(float);
-    if (lds > 160 * 1024) { set_error("lbs_backward_joints: J = %d needs %d B of LDS (J <= 140)", a->J, lds); return AG_ERR_INVALID_ARGUMENT; }
+    if (a->J > kJointGradMaxJ) { set_error("lbs_backward_joints: J = %d, the joint gradient takes J <= %d", a->J, kJointGradMaxJ); return AG_ERR_INVALID_ARGUMENT; }
+    const int lds = (4 * 64 * a->J + 4 * 64 * 12) * (int)sizeof(float);         // <= 155648 B at J = 140
     float* slabs = static_cast<float*>(workspace);
     if (g_positions || g_rotations) {            // the position / rotation gradients: ag_lbs_backward's own launch, bit for bit
         if (!g_positions || !g_rotations) { set_error("lbs_backward_joints: dL_dpositions and dL_drotations are both set or both NULL"); return AG_ERR_INVALID_ARGUMENT; }
         if ((rc = ag_lbs_backward(a, g_positions, g_rotations, stream))) return rc;
     }
     if (a->K > 0) {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lbs_backward_joints_kernel<true>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if ((rc = allow_lds(reinterpret_cast<const void*>(&lbs_backward_joints_kernel<true>), lds, "lbs_backward_joints_kernel (LDS size)"))) return rc;
         hipLaunchKernelGGL(lbs_backward_joints_kernel<true>, dim3(nslab), dim3(256), lds, s, *a, slabs);
     } else {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lbs_backward_joints_kernel<false>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if ((rc = allow_lds(reinterpret_cast<const void*>(&lbs_backward_joints_kernel<false>), lds, "lbs_backward_joints_kernel (LDS size)"))) return rc;
         hipLaunchKernelGGL(lbs_backward_joints_kernel<false>, dim3(nslab), dim3(256), lds, s, *a, slabs);
     }
     if ((rc = check_hip(hipGetLastError(), "lbs_backward_joints_kernel"))) return rc;

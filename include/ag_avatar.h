@@ -65,7 +65,11 @@ int ag_gather_activate_backward(const AgGatherArgs* fwd_inputs_and_grads, float*
 /* Linear-blend skinning of positions and rotations (quaternions as (r, i, j, k)). */
 typedef struct AgLbsArgs {
     int32_t N;
-    int32_t J;                  /* joints (55 for SMPL-X); 1 <= J <= 256 */
+    int32_t J;                  /* joints (55 for SMPL-X).  Sparse rows (K > 0): 1 <= J <= 256 (uint8 indices).  Dense rows (K == 0):
+                                 * the kernels stage 4 * 64 * J floats in LDS, so 1024 * J bytes must fit the device's LDS per
+                                 * workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock): 1 <= J <= 160 on gfx950.  A larger dense J
+                                 * is refused with AG_ERR_INVALID_ARGUMENT before any launch; ag_last_error() names the largest
+                                 * dense J of the device.  ag_lbs_backward_joints: J <= 140 in both forms (see below). */
     const float* lbs;           /* [N, J] blend weights */
     const float* jnt_mats;      /* [J, 4, 4] cano2live joint matrices, row-major */
     const float* positions;     /* [N,3] */
@@ -93,7 +97,8 @@ int ag_lbs_backward(const AgLbsArgs* fwd_inputs_and_grads, float* dL_dpositions 
  * ag_lbs_backward's own launch, so they are its bits; the joint gradient is a second pass over the Gaussians.  The sum over them is
  * deterministic (per-workgroup slabs in `workspace`, combined in a fixed order by a second launch, no float atomics), and the sparse
  * form gives the dense form's bits: a skipped term is + 0 * G_n.  workspace: device memory of at least
- * ag_lbs_backward_joints_workspace_bytes(N, J) bytes.  Dense and sparse rows: J <= 140 (LDS).
+ * ag_lbs_backward_joints_workspace_bytes(N, J) bytes.  Dense and sparse rows: J <= 140 (the pass keeps (256 J + 3072) * 4 bytes of LDS,
+ * 155648 B at J = 140); a larger J is refused with AG_ERR_INVALID_ARGUMENT before any launch.
  */
 size_t ag_lbs_backward_joints_workspace_bytes(int32_t N, int32_t J);
 int ag_lbs_backward_joints(const AgLbsArgs* fwd_inputs_and_grads, float* dL_dpositions /*[N,3] or NULL*/,
