@@ -158,6 +158,13 @@ class AgMeshRasterArgs(ctypes.Structure):     # include/ag_subject_maps.h
                 + [("workspace_bytes", c_sz)])
 
 
+class AgMeshQueryArgs(ctypes.Structure):      # include/ag_mesh_query.h
+    _fields_ = ([(n, c_i32) for n in ("N", "V", "F", "gx", "gy", "gz", "walk", "reserved")]
+                + [(n, c_vp) for n in ("points", "axis_x", "axis_y", "axis_z", "vertices", "faces", "dist2", "face_id", "bary", "feature",
+                                       "workspace")]
+                + [("workspace_bytes", c_sz)])
+
+
 # every symbol include/*.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ag_abi_version", ctypes.c_int, []),
@@ -256,6 +263,10 @@ SYMBOLS = [
                                     ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     # include/ag_weight_volume.h
     ("ag_weight_volume_sample", ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, ctypes.c_int64, ctypes.POINTER(c_f), c_vp, c_vp]),
+    # include/ag_mesh_query.h
+    ("ag_mesh_closest_point_workspace_bytes", c_sz, [c_i32]),
+    ("ag_mesh_closest_point", ctypes.c_int, [ctypes.POINTER(AgMeshQueryArgs), c_vp]),
+    ("ag_mesh_pseudonormal_sign", ctypes.c_int, [ctypes.POINTER(AgMeshQueryArgs), c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_targets.h
     ("ag_prepare_targets", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_styleunet.h

@@ -190,7 +190,8 @@ def knn_log_scale(points: torch.Tensor) -> torch.Tensor:
 
 
 def canonical_maps(vertices: torch.Tensor, faces: torch.Tensor, normals: torch.Tensor, lbs_weights: Optional[torch.Tensor] = None,
-                   size: int = 1024, *, weight_volume=None, center: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                   size: int = 1024, *, weight_volume=None, center: Optional[torch.Tensor] = None,
+                   lbs_rule: str = "rendered") -> Dict[str, torch.Tensor]:
     """The canonical part of ``gen_pos_maps.py`` (:75, :93-134) plus the scale initialiser.  Without the keywords: the
     SMPL-X-as-template branch, the mesh IS the body and ``lbs_weights`` [V, J] are interpolated.  With ``weight_volume`` (a
     ``weight_volume.WeightVolume``): the ``using_template`` branch (:79-82, :128-130), the mesh is the clothed template,
@@ -200,8 +201,10 @@ def canonical_maps(vertices: torch.Tensor, faces: torch.Tensor, normals: torch.T
     :88), and that is the ``center`` ``gen_weight_volume.py:139`` stores.  Returns
 
     ``cano_smpl_pos_map`` / ``cano_smpl_nml_map`` [S, 2S, 3] (front | back, zeros where empty), ``mask`` [S, 2S] (``|pos| > 0``),
-    ``init_pts_lbs`` [N, J] in ``map[mask]`` order -- interpolated with the RENDERED face and its barycentrics, where the reference
-    searches the nearest face of the rendered point --, ``log_scale`` [N], ``cano_center`` [3], and ``face_id`` / ``bary``."""
+    ``init_pts_lbs`` [N, J] in ``map[mask]`` order, ``log_scale`` [N], ``cano_center`` [3], and ``face_id`` / ``bary``.
+    ``lbs_rule`` (the per-vertex branch only): ``'rendered'`` interpolates the weights with the RENDERED face and its barycentrics;
+    ``'nearest'`` is the reference's rule (:132), the nearest face of the rendered point (``mesh_query.interpolate_lbs``): the same
+    weights up to rounding, at the cost of a search over all faces per point."""
     v = _dev(vertices, "vertices", torch.float32, 3)
     f = _dev(faces, "faces", torch.int32, 3)
     n = _dev(normals, "normals", torch.float32, 3)
@@ -211,6 +214,8 @@ def canonical_maps(vertices: torch.Tensor, faces: torch.Tensor, normals: torch.T
             raise ValueError("normals [V, 3] and lbs_weights [V, J] must have one row per vertex")
     if n.shape[0] != v.shape[0]:
         raise ValueError("normals [V, 3] and lbs_weights [V, J] must have one row per vertex")
+    if lbs_rule not in ("rendered", "nearest"):
+        raise ValueError(f"lbs_rule must be 'rendered' or 'nearest', got {lbs_rule!r}")
     S = int(size)
     if center is None:
         center = 0.5 * (v.amin(0) + v.amax(0)) if weight_volume is None else weight_volume.center       # gen_pos_maps.py:75
@@ -229,6 +234,9 @@ def canonical_maps(vertices: torch.Tensor, faces: torch.Tensor, normals: torch.T
     init_points = pos.reshape(-1, 3)[pix.long()]
     if weight_volume is not None:
         lbs = weight_volume.forward_weight(init_points)                         # :129-130
+    elif lbs_rule == "nearest":
+        from .mesh_query import interpolate_lbs
+        lbs = interpolate_lbs(init_points, v, f, w)                             # :132
     else:
         lbs = resolve(face_id, bary, f, w, pix=pix)
     return {"cano_smpl_pos_map": pos, "cano_smpl_nml_map": nml, "mask": mask, "init_pts_lbs": lbs,

@@ -6,7 +6,10 @@ weights of a template's canonical points are trilinear samples of it (``gen_pos_
 arrays to [1, J, X, Y, Z] for ``F.grid_sample``; here they stay channel-last as the file stores them, which is the layout the kernel
 reads (one grid node = one contiguous row) and needs no second copy of a 461 MB volume.
 
-The volume file is an INPUT: building it needs an external Poisson solver and libigl's signed distance and is out of scope.
+The Poisson-DIFFUSED volume is an input: it needs the reference's external solver and is out of scope.  What a closest-point query
+gives is built here (``WeightVolume.from_body_mesh``, ``include/ag_mesh_query.h``): the bounds, ``center``, the nearest-surface
+``ori_weight_volume`` and ``sdf_volume`` of ``gen_data/gen_weight_volume.py:136-170``, with the nearest-surface weights standing in for
+the diffused ones; ``WeightVolume.save`` writes the reference's file.
 No gradient with respect to ``pts`` (nor the volume): the outputs never require grad.  The reference differentiates ``forward_weight``
 only when it trains a template network, which this package does not do.  ``forward_weight_grad`` is omitted: the reference's own
 ``base_gradient_volume`` it reads is commented out (``volume.py:70``).
@@ -37,10 +40,35 @@ def _volume(t, name: str, device) -> torch.Tensor:
     return t.contiguous()
 
 
+def body_bounds(min_xyz: np.ndarray, max_xyz: np.ndarray):
+    """(volume_bounds [2, 3], center [3], smpl_bounds [2, 3]) from the body's bounding box, the expressions of
+    ``gen_weight_volume.py:136-150``: a cube of 1.1 x the longest extent about the box's centre, and the box grown by 5 / 5 / 15 cm."""
+    min_xyz = np.array(min_xyz).astype(np.float32)
+    max_xyz = np.array(max_xyz).astype(np.float32)
+    max_len = 1.1 * (max_xyz - min_xyz).max()
+    center = 0.5 * (min_xyz + max_xyz)
+    volume_bounds = np.stack([center - 0.5 * max_len, center + 0.5 * max_len], 0)
+    min_xyz[:2] -= 0.05
+    max_xyz[:2] += 0.05
+    min_xyz[2] -= 0.15
+    max_xyz[2] += 0.15
+    smpl_bounds = np.stack([min_xyz, max_xyz], 0)
+    return volume_bounds.astype(np.float32), center.astype(np.float32), smpl_bounds.astype(np.float32)
+
+
+def grid_axes(volume_bounds: np.ndarray, res):
+    """The three node axes ``float32(np.linspace(lo_k, hi_k, res_k))`` (``gen_weight_volume.py:88-90``, rounded to the float32 the
+    device computes in)."""
+    return [np.float32(np.linspace(volume_bounds[0, k], volume_bounds[1, k], res[k])) for k in range(3)]
+
+
 class WeightVolume:
     """``diff_weight_volume`` / ``ori_weight_volume`` [X, Y, Z, J], optional ``sdf_volume`` [X, Y, Z] or [X, Y, Z, 1], ``volume_bounds``
     [2, 3] (lo, hi), ``center`` [3] (of the SMPL-X body: ``gen_weight_volume.py:139``), ``smpl_bounds`` [2, 3]; arrays or tensors.
-    ``device`` defaults to the device of ``diff_weight_volume``."""
+    ``device`` defaults to the device of ``diff_weight_volume``.  ``diffused``: whether ``diff_weight_volume`` holds Poisson-diffused
+    weights (a loaded file) or is the nearest-surface ``ori_weight_volume`` itself (``from_body_mesh``)."""
+
+    diffused = True
 
     def __init__(self, diff_weight_volume, ori_weight_volume, volume_bounds, center, smpl_bounds, sdf_volume=None, device=None):
         if device is None:
@@ -79,6 +107,51 @@ class WeightVolume:
         with np.load(path) as data:
             return cls(data["diff_weight_volume"], data["ori_weight_volume"], data["volume_bounds"], data["center"], data["smpl_bounds"],
                        sdf_volume=data["sdf_volume"] if "sdf_volume" in data else None, device=device)
+
+    @classmethod
+    def from_body_mesh(cls, vertices: torch.Tensor, faces: torch.Tensor, lbs_weights: torch.Tensor, res=128) -> "WeightVolume":
+        """The volume of a body mesh (the canonical SMPL-X: ``vertices`` [V, 3], ``faces`` [F, 3], ``lbs_weights`` [V, J], on the GPU)
+        without the Poisson solver: ``gen_weight_volume.py:136-170`` minus ``diff_weights``.  Bounds, ``center`` and ``smpl_bounds``
+        are the reference's numpy expressions on the host; the grid axes are ``float32(np.linspace(lo_k, hi_k, res_k))``, uploaded as
+        they are and read by the kernel (node (i, j, k) = (x_i, y_j, z_k), arrays [X, Y, Z, ...]); ``ori_weight_volume`` holds the
+        weights interpolated at each node's closest point of the mesh, ``sdf_volume`` the signed distance, positive inside (:167;
+        ``mesh_query``: pseudonormal sign, exact for a closed, consistently wound mesh).  ``res``: an int or (X, Y, Z).
+
+        ``diff_weight_volume`` IS ``ori_weight_volume`` (one tensor, 461 MB at 128^3 x 55, not two) and ``diffused`` is ``False``:
+        these are NEAREST-SURFACE weights, discontinuous across the body's medial surface (between the legs, under the arms), where
+        the reference's are Poisson-diffused and smooth.  Near the body surface, where a tight template lies, the two agree."""
+        from . import mesh_query
+        from .subject_maps import _dev, resolve
+        v = _dev(vertices, "vertices", torch.float32, 3)
+        f = _dev(faces, "faces", torch.int32, 3)
+        w = _dev(lbs_weights, "lbs_weights", torch.float32)
+        if w.dim() != 2 or w.shape[0] != v.shape[0] or v.shape[0] == 0 or f.shape[0] == 0:
+            raise ValueError("from_body_mesh needs a non-empty mesh and lbs_weights [V, J] with one row per vertex")
+        res = (int(res),) * 3 if np.isscalar(res) else tuple(int(r) for r in res)
+        if len(res) != 3 or min(res) < 2:
+            raise ValueError(f"res must be an int or (X, Y, Z), each >= 2, got {res}")
+        volume_bounds, center, smpl_bounds = body_bounds(v.amin(0).cpu().numpy(), v.amax(0).cpu().numpy())
+        axes = grid_axes(volume_bounds, res)
+        sdf, face_id, bary = mesh_query.grid_signed_distance([torch.from_numpy(a).to(v.device) for a in axes], v, f)
+        ori = resolve(face_id, bary, f, w).view(res + (w.shape[1],))
+        vol = cls(ori, ori, volume_bounds, center, smpl_bounds, sdf_volume=(-sdf).view(res), device=v.device)
+        vol.diffused = False
+        return vol
+
+    def save(self, path: str, alias_diff: bool = True) -> None:
+        """Write ``cano_weight_volume.npz`` with the key names, shapes and dtypes of ``gen_weight_volume.py:164-170`` (float32;
+        ``sdf_volume`` [X, Y, Z]): what ``load`` and the reference's ``CanoBlendWeightVolume`` read.  ``alias_diff=False`` leaves
+        ``diff_weight_volume`` out of the file of a volume that is not ``diffused``, for users who will add their own (the file
+        cannot be loaded until they have)."""
+        host = lambda t: t.detach().cpu().numpy().astype(np.float32)  # noqa: E731
+        arrays = {"ori_weight_volume": host(self.ori_weight_volume), "volume_bounds": host(self.volume_bounds),
+                  "smpl_bounds": host(self.smpl_bounds), "center": host(self.center)}
+        if self.diffused or alias_diff:
+            arrays["diff_weight_volume"] = arrays["ori_weight_volume"] if self.diff_weight_volume is self.ori_weight_volume \
+                else host(self.diff_weight_volume)
+        if self.smpl_sdf_volume is not None:
+            arrays["sdf_volume"] = host(self.smpl_sdf_volume)[..., 0]
+        np.savez(path, **arrays)
 
     def _sample(self, volume: torch.Tensor, pts: torch.Tensor, requires_scale: bool) -> torch.Tensor:
         if not isinstance(pts, torch.Tensor) or not pts.is_cuda:
