@@ -267,6 +267,11 @@ SYMBOLS = [
     ("ag_mesh_closest_point_workspace_bytes", c_sz, [c_i32]),
     ("ag_mesh_closest_point", ctypes.c_int, [ctypes.POINTER(AgMeshQueryArgs), c_vp]),
     ("ag_mesh_pseudonormal_sign", ctypes.c_int, [ctypes.POINTER(AgMeshQueryArgs), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # include/ag_weight_diffuse.h
+    ("ag_weight_diffuse_workspace_bytes", c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    ("ag_weight_diffuse_apply", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_f), c_vp, c_vp]),
+    ("ag_weight_diffuse_init", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_f)] + [c_vp] * 5 + [c_sz, c_vp, c_vp, c_vp]),
+    ("ag_weight_diffuse_iterate", ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_f), c_i32] + [c_vp] * 5 + [c_sz, c_vp, c_vp]),
     # include/ag_targets.h
     ("ag_prepare_targets", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_styleunet.h

@@ -6,10 +6,13 @@ weights of a template's canonical points are trilinear samples of it (``gen_pos_
 arrays to [1, J, X, Y, Z] for ``F.grid_sample``; here they stay channel-last as the file stores them, which is the layout the kernel
 reads (one grid node = one contiguous row) and needs no second copy of a 461 MB volume.
 
-The Poisson-DIFFUSED volume is an input: it needs the reference's external solver and is out of scope.  What a closest-point query
-gives is built here (``WeightVolume.from_body_mesh``, ``include/ag_mesh_query.h``): the bounds, ``center``, the nearest-surface
-``ori_weight_volume`` and ``sdf_volume`` of ``gen_data/gen_weight_volume.py:136-170``, with the nearest-surface weights standing in for
-the diffused ones; ``WeightVolume.save`` writes the reference's file.
+Everything in the file can be built here.  ``WeightVolume.from_body_mesh`` (``include/ag_mesh_query.h``) gives what a closest-point
+query gives: the bounds, ``center``, the nearest-surface ``ori_weight_volume`` and ``sdf_volume`` of
+``gen_data/gen_weight_volume.py:136-170``.  ``WeightVolume.diffuse`` (``include/ag_weight_diffuse.h``) then extends the weights near the
+body surface smoothly into the whole grid, which is what ``diff_weight_volume`` is for; ``WeightVolume.save`` writes the reference's
+file: ``WeightVolume.from_body_mesh(v, f, w).diffuse().save(path)``.  The reference produces its ``diff_weight_volume`` with an external
+program (PointInterpolant: values and gradients fitted with B-splines on an adaptive octree).  ``diffuse`` is NOT that program and
+claims no equality with its output: it is the discrete harmonic extension defined by ``diffuse_weights`` below.
 No gradient with respect to ``pts`` (nor the volume): the outputs never require grad.  The reference differentiates ``forward_weight``
 only when it trains a template network, which this package does not do.  ``forward_weight_grad`` is omitted: the reference's own
 ``base_gradient_volume`` it reads is commented out (``volume.py:70``).
@@ -62,13 +65,127 @@ def grid_axes(volume_bounds: np.ndarray, res):
     return [np.float32(np.linspace(volume_bounds[0, k], volume_bounds[1, k], res[k])) for k in range(3)]
 
 
+def stencil_weights(spacing) -> np.ndarray:
+    """``w_k = (h_min / h_k)^2`` as float32 [3]: 1 on a cubic grid, so the problem does not depend on the grid's scale."""
+    h = np.asarray([float(x) for x in spacing], np.float64)
+    if h.shape != (3,) or not (np.isfinite(h).all() and (h > 0).all()):
+        raise ValueError(f"spacing must be three positive node spacings, got {spacing}")
+    return ((h.min() / h) ** 2).astype(np.float32)
+
+
+def _diffuse_args(target, fixed):
+    if not (isinstance(target, torch.Tensor) and isinstance(fixed, torch.Tensor) and target.is_cuda and fixed.is_cuda):
+        raise ValueError("target and fixed must be tensors on the GPU (there is no host path)")
+    if target.device != fixed.device:
+        raise ValueError(f"target is on {target.device}, fixed on {fixed.device}")
+    if target.dim() != 4 or min(target.shape[:3]) < 2 or target.shape[3] < 1:
+        raise ValueError(f"target must be [X, Y, Z, J] with X, Y, Z >= 2 and J >= 1, got {tuple(target.shape)}")
+    if fixed.dtype != torch.bool or tuple(fixed.shape) != tuple(target.shape[:3]):
+        raise ValueError(f"fixed must be a bool mask of shape {tuple(target.shape[:3])}, got {fixed.dtype} {tuple(fixed.shape)}")
+    return target.detach().to(torch.float32).contiguous(), fixed.contiguous()
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def diffusion_operator(values: torch.Tensor, fixed: torch.Tensor, spacing) -> torch.Tensor:
+    """``A values`` of ``include/ag_weight_diffuse.h``: at every node that is not ``fixed`` the weighted sum over the three axes of
+    ``(u - u_lower) + (u - u_upper)`` (neighbours read as given, one outside the grid dropped), 0 on fixed nodes."""
+    v, m = _diffuse_args(values, fixed)
+    w = (ctypes.c_float * 3)(*stencil_weights(spacing).tolist())
+    X, Y, Z, J = v.shape
+    out = torch.empty_like(v)
+    with _lib.on_device(v.device):
+        _lib.check(_lib.lib().ag_weight_diffuse_apply(_ptr(v), _ptr(m), X, Y, Z, J, w, _ptr(out),
+                                                      ctypes.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)), "ag_weight_diffuse_apply")
+    return out
+
+
+def diffuse_weights(target: torch.Tensor, fixed: torch.Tensor, spacing, *, tol: float = 1e-5, max_iter: Optional[int] = None,
+                    check_every: int = 16):
+    """The discrete harmonic extension of ``target`` [X, Y, Z, J] from the nodes of the bool mask ``fixed`` [X, Y, Z] into all the
+    others (``include/ag_weight_diffuse.h``); ``spacing``: the three node spacings.  Returns ``(u, info)``:
+
+    * ``u = target`` on fixed nodes, bit for bit;
+    * at every other node, for every channel, ``sum_k w_k [(u - u_lower_k) + (u - u_upper_k)] = 0`` with ``w_k = (h_min / h_k)^2``
+      and a neighbour outside the grid dropped (no flux through the cube's faces).
+
+    So ``u`` stays within the range of the fixed values of its channel (maximum principle), rows that sum to 1 on the fixed nodes sum
+    to 1 everywhere, and ``u`` is continuous where nearest-surface weights jump.  ``u`` is the raw solution: not clipped, not
+    renormalised.  This is this project's definition; it is not the reference's external PointInterpolant fit and claims no
+    equality with it.
+
+    Solver: conjugate gradients on the free nodes, all channels in lockstep, each with its own scalars, so each is an exact CG of
+    its own system; ``check_every`` iterations are enqueued at a time and the [J] residuals read in between.  It stops when every
+    channel has ``|r_j| <= tol |b_j|``.  A channel whose fixed values are all zero stays exactly zero.
+    ``max_iter`` defaults to ``20 * max(X, Y, Z)``: plain CG needed about 5.6 iterations per node along the longest edge on CPU
+    trials of this problem at 16^3 to 64^3 (the count grows with the distance, in nodes, that the fixed values must travel), and 3.5 x
+    that leaves room for an anisotropic grid or a thin band without letting a stalled solve run on.
+
+    ``info``: ``iterations``, ``rel_residual`` [J] (the recurrence's ``|r_j| / |b_j|``, 0 where ``b_j = 0``), ``true_rel_residual`` [J]
+    (``|A u|_j / |b_j|`` from one more application of the operator to the returned ``u``), ``converged``.
+    No fixed node: ``ValueError`` (the extension is undefined).  All nodes fixed: ``target`` itself, 0 iterations."""
+    t, m = _diffuse_args(target, fixed)
+    w_host = stencil_weights(spacing)
+    if not (tol > 0) or int(check_every) < 1:
+        raise ValueError(f"tol must be positive and check_every at least 1, got {tol}, {check_every}")
+    X, Y, Z, J = t.shape
+    n_fixed = int(m.sum())
+    if n_fixed == 0:
+        raise ValueError("no fixed node: the harmonic extension is undefined")
+    zeros = torch.zeros(J, dtype=torch.float64)
+    if n_fixed == m.numel():
+        return target, {"iterations": 0, "rel_residual": zeros, "true_rel_residual": zeros.clone(), "converged": True}
+    if max_iter is None:
+        max_iter = 20 * max(X, Y, Z)
+    max_iter, check_every = int(max_iter), int(check_every)
+    L = _lib.lib()
+    w = (ctypes.c_float * 3)(*w_host.tolist())
+    dev = t.device
+    x, r, p, ap = (torch.empty_like(t) for _ in range(4))
+    n_ws = int(L.ag_weight_diffuse_workspace_bytes(X, Y, Z, J))
+    if n_ws == 0:
+        raise ValueError(f"a grid of {X} x {Y} x {Z} nodes is outside what ag_weight_diffuse takes (fewer than 2^31 nodes)")
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=dev)
+    bb = torch.empty(J, dtype=torch.float32, device=dev)
+    rr = torch.empty(J, dtype=torch.float32, device=dev)
+
+    def rel(num, den):
+        num, den = num.double().cpu(), den.double().cpu()
+        return torch.where(den > 0, (num / den.clamp_min(1e-300)).sqrt(), num.sqrt())
+
+    with _lib.on_device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(L.ag_weight_diffuse_init(_ptr(t), _ptr(m), X, Y, Z, J, w, _ptr(x), _ptr(r), _ptr(p), _ptr(ap), _ptr(ws), n_ws, _ptr(bb), _ptr(rr),
+                                            stream), "ag_weight_diffuse_init")
+        bb_host = bb.double().cpu()
+        iterations = 0
+        while True:
+            rr_host = rr.double().cpu()
+            converged = bool((rr_host <= (tol * tol) * bb_host).all())
+            if converged or iterations >= max_iter:
+                break
+            n = min(check_every, max_iter - iterations)
+            _lib.check(L.ag_weight_diffuse_iterate(_ptr(m), X, Y, Z, J, w, n, _ptr(x), _ptr(r), _ptr(p), _ptr(ap), _ptr(ws), n_ws, _ptr(rr), stream),
+                       "ag_weight_diffuse_iterate")
+            iterations += n
+        u = torch.where(m[..., None], t, x)
+        _lib.check(L.ag_weight_diffuse_apply(_ptr(u), _ptr(m), X, Y, Z, J, w, _ptr(ap), stream), "ag_weight_diffuse_apply")
+        true_sq = ap.double().square().sum((0, 1, 2))
+    info = {"iterations": iterations, "rel_residual": rel(rr, bb), "true_rel_residual": rel(true_sq, bb), "converged": converged}
+    return u, info
+
+
 class WeightVolume:
     """``diff_weight_volume`` / ``ori_weight_volume`` [X, Y, Z, J], optional ``sdf_volume`` [X, Y, Z] or [X, Y, Z, 1], ``volume_bounds``
     [2, 3] (lo, hi), ``center`` [3] (of the SMPL-X body: ``gen_weight_volume.py:139``), ``smpl_bounds`` [2, 3]; arrays or tensors.
-    ``device`` defaults to the device of ``diff_weight_volume``.  ``diffused``: whether ``diff_weight_volume`` holds Poisson-diffused
-    weights (a loaded file) or is the nearest-surface ``ori_weight_volume`` itself (``from_body_mesh``)."""
+    ``device`` defaults to the device of ``diff_weight_volume``.  ``diffused``: whether ``diff_weight_volume`` holds diffused weights
+    (a loaded file, or the result of ``diffuse``) or is the nearest-surface ``ori_weight_volume`` itself (``from_body_mesh``).
+    ``diffusion``: what ``diffuse`` recorded of its solve (``None`` otherwise)."""
 
     diffused = True
+    diffusion = None
 
     def __init__(self, diff_weight_volume, ori_weight_volume, volume_bounds, center, smpl_bounds, sdf_volume=None, device=None):
         if device is None:
@@ -111,7 +228,7 @@ class WeightVolume:
     @classmethod
     def from_body_mesh(cls, vertices: torch.Tensor, faces: torch.Tensor, lbs_weights: torch.Tensor, res=128) -> "WeightVolume":
         """The volume of a body mesh (the canonical SMPL-X: ``vertices`` [V, 3], ``faces`` [F, 3], ``lbs_weights`` [V, J], on the GPU)
-        without the Poisson solver: ``gen_weight_volume.py:136-170`` minus ``diff_weights``.  Bounds, ``center`` and ``smpl_bounds``
+        before diffusion: ``gen_weight_volume.py:136-170`` minus ``diff_weights``.  Bounds, ``center`` and ``smpl_bounds``
         are the reference's numpy expressions on the host; the grid axes are ``float32(np.linspace(lo_k, hi_k, res_k))``, uploaded as
         they are and read by the kernel (node (i, j, k) = (x_i, y_j, z_k), arrays [X, Y, Z, ...]); ``ori_weight_volume`` holds the
         weights interpolated at each node's closest point of the mesh, ``sdf_volume`` the signed distance, positive inside (:167;
@@ -119,7 +236,8 @@ class WeightVolume:
 
         ``diff_weight_volume`` IS ``ori_weight_volume`` (one tensor, 461 MB at 128^3 x 55, not two) and ``diffused`` is ``False``:
         these are NEAREST-SURFACE weights, discontinuous across the body's medial surface (between the legs, under the arms), where
-        the reference's are Poisson-diffused and smooth.  Near the body surface, where a tight template lies, the two agree."""
+        diffused ones are smooth.  Near the body surface, where a tight template lies, the two agree; for a skirt, a coat hem or a
+        loose sleeve call ``diffuse()`` on the result."""
         from . import mesh_query
         from .subject_maps import _dev, resolve
         v = _dev(vertices, "vertices", torch.float32, 3)
@@ -136,6 +254,36 @@ class WeightVolume:
         ori = resolve(face_id, bary, f, w).view(res + (w.shape[1],))
         vol = cls(ori, ori, volume_bounds, center, smpl_bounds, sdf_volume=(-sdf).view(res), device=v.device)
         vol.diffused = False
+        return vol
+
+    def diffuse(self, band: Optional[float] = None, *, tol: float = 1e-5, max_iter: Optional[int] = None) -> "WeightVolume":
+        """A NEW volume whose ``diff_weight_volume`` is ``ori_weight_volume`` diffused from the body surface into the whole grid
+        (``diffuse_weights``); ``ori_weight_volume``, the SDF and the bounds are shared with this one, ``diffused`` is ``True`` and
+        ``diffusion`` holds the solve's ``info`` and the ``band`` used.
+
+        Fixed nodes: ``|sdf_volume| <= band``, where the nearest-surface weights are the right ones.  ``band`` is in the units of the
+        bounds (metres) and defaults to 1.5 x the largest node spacing, which keeps at least one layer of nodes on either side of the
+        surface wherever it passes -- a choice of this project, not a value of the reference.  The solution is clipped to [0, 1] and
+        each row divided by its sum (``gen_weight_volume.py:131-132``); a row that sums to 0 stays 0.
+        ``RuntimeError`` if the solve does not reach ``tol`` within ``max_iter`` iterations."""
+        if self.smpl_sdf_volume is None:
+            raise ValueError("diffuse needs the sdf_volume: it says which nodes lie near the body surface")
+        spacing = [float(h) for h in self.voxel_size.cpu()]
+        if band is None:
+            band = 1.5 * max(spacing)
+        band = float(band)
+        fixed = (self.smpl_sdf_volume[..., 0].abs() <= band).contiguous()
+        u, info = diffuse_weights(self.ori_weight_volume, fixed, spacing, tol=tol, max_iter=max_iter)
+        if not info["converged"]:
+            raise RuntimeError(f"the diffusion did not reach tol = {tol} in {info['iterations']} iterations "
+                               f"(worst relative residual {float(info['rel_residual'].max()):.3e}); raise max_iter")
+        u = u.clamp(0.0, 1.0)
+        total = u.sum(-1, keepdim=True)
+        u = torch.where(total > 0, u / torch.where(total > 0, total, torch.ones_like(total)), torch.zeros_like(u))
+        vol = WeightVolume(u, self.ori_weight_volume, self.volume_bounds, self.center, self.smpl_bounds, sdf_volume=self.smpl_sdf_volume,
+                           device=u.device)
+        vol.diffused = True
+        vol.diffusion = dict(info, band=band, fixed_nodes=int(fixed.sum()))
         return vol
 
     def save(self, path: str, alias_diff: bool = True) -> None:
