@@ -13,6 +13,8 @@ body surface smoothly into the whole grid, which is what ``diff_weight_volume`` 
 file: ``WeightVolume.from_body_mesh(v, f, w).diffuse().save(path)``.  The reference produces its ``diff_weight_volume`` with an external
 program (PointInterpolant: values and gradients fitted with B-splines on an adaptive octree).  ``diffuse`` is NOT that program and
 claims no equality with its output: it is the discrete harmonic extension defined by ``diffuse_weights`` below.
+The way back, posed point -> canonical point, reads the volume at its NEAREST node together with its Sobel gradient
+(``WeightVolume.gradient_volume``, ``WeightVolume.root_find``; ``include/ag_inverse_skinning.h``, ``inverse_skinning.py``).
 No gradient with respect to ``pts`` (nor the volume): the outputs never require grad.  The reference differentiates ``forward_weight``
 only when it trains a template network, which this package does not do.  ``forward_weight_grad`` is omitted: the reference's own
 ``base_gradient_volume`` it reads is commented out (``volume.py:70``).
@@ -330,3 +332,33 @@ class WeightVolume:
         if self.smpl_sdf_volume is None:
             raise ValueError("this WeightVolume was built without an sdf_volume")
         return self._sample(self.smpl_sdf_volume, pts, requires_scale)
+
+    def _which(self, volume_type: str) -> torch.Tensor:
+        return self.diff_weight_volume if volume_type == "diff" else self.ori_weight_volume
+
+    def _spacing_host(self):
+        return (ctypes.c_float * 3)(*self.voxel_size.cpu().tolist())
+
+    def gradient_volume(self, volume_type: str = "diff") -> torch.Tensor:
+        """The Sobel gradient [X, Y, Z, J, 3] of the weight volume (``include/ag_inverse_skinning.h``; the reference's
+        ``compute_gradient_volume``, ``network/volume.py:9-39``, in its [X, Y, Z, J * 3] layout): 1.38 GB at 128^3 x 55.  ``root_find``
+        does not need it; pass it as ``grad_volume`` to read the rows instead of forming them on the fly (identical bits)."""
+        vol = self._which(volume_type)
+        X, Y, Z, J = vol.shape
+        out = torch.empty((X, Y, Z, J, 3), dtype=torch.float32, device=vol.device)
+        with _lib.on_device(vol.device):
+            _lib.check(_lib.lib().ag_weight_volume_gradient(_ptr(vol), X, Y, Z, J, self._spacing_host(), _ptr(out),
+                                                            ctypes.c_void_p(torch.cuda.current_stream(vol.device).cuda_stream)),
+                       "ag_weight_volume_gradient")
+        return out
+
+    def root_find(self, posed_pts: torch.Tensor, cano_init: torch.Tensor, jnt_mats: torch.Tensor, *, active: Optional[torch.Tensor] = None,
+                  lam: float = 0.1, iterations: int = 10, volume_type: str = "diff", grad_volume: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Canonical points ``xc`` with ``sum_j w_j(xc) (A_j xc) = posed_pts``: ``iterations`` damped Newton steps from ``cano_init``
+        through the weights at the NEAREST node of the volume and their Sobel gradient (``include/ag_inverse_skinning.h``; the
+        reference's ``root_finding.cu``).  ``posed_pts``, ``cano_init`` [B, N, 3] (or [N, 3] with ``jnt_mats`` [J, 4, 4] or [1, J, 4, 4]),
+        ``jnt_mats`` [B, J, 4, 4] canonical -> posed, each batch its own; ``active`` [B, N] bool: points with ``False`` come back as
+        ``cano_init``.  Each step is clamped to 1 cm per axis, so the result lies within ``iterations`` cm of ``cano_init``.
+        No gradient: the reference runs this step under ``no_grad``."""
+        from . import inverse_skinning
+        return inverse_skinning._root_find(self, posed_pts, cano_init, jnt_mats, active, lam, iterations, volume_type, grad_volume)
