@@ -277,6 +277,11 @@ SYMBOLS = [
     ("ag_inverse_skinning_init", ctypes.c_int, [c_vp] * 6 + [c_i32, ctypes.c_int64, c_i32, c_vp]),
     ("ag_inverse_skinning_root_find", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_f), ctypes.POINTER(c_f)] + [c_vp] * 5
      + [c_i32, ctypes.c_int64, c_f, c_i32, c_vp]),
+    # include/ag_isosurface.h
+    ("ag_isosurface_workspace_bytes", c_sz, [c_i32, c_i32, c_i32]),
+    ("ag_isosurface_count", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f, c_vp, c_sz, c_vp, c_vp]),
+    ("ag_isosurface_emit", ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_vp, c_sz, c_vp, c_i32, c_vp, c_i32,
+                                          c_vp]),
     # include/ag_targets.h
     ("ag_prepare_targets", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_styleunet.h

@@ -15,6 +15,7 @@ program (PointInterpolant: values and gradients fitted with B-splines on an adap
 claims no equality with its output: it is the discrete harmonic extension defined by ``diffuse_weights`` below.
 The way back, posed point -> canonical point, reads the volume at its NEAREST node together with its Sobel gradient
 (``WeightVolume.gradient_volume``, ``WeightVolume.root_find``; ``include/ag_inverse_skinning.h``, ``inverse_skinning.py``).
+``WeightVolume.isosurface`` turns the SDF back into a mesh (``isosurface.py``, ``include/ag_isosurface.h``).
 No gradient with respect to ``pts`` (nor the volume): the outputs never require grad.  The reference differentiates ``forward_weight``
 only when it trains a template network, which this package does not do.  ``forward_weight_grad`` is omitted: the reference's own
 ``base_gradient_volume`` it reads is commented out (``volume.py:70``).
@@ -332,6 +333,15 @@ class WeightVolume:
         if self.smpl_sdf_volume is None:
             raise ValueError("this WeightVolume was built without an sdf_volume")
         return self._sample(self.smpl_sdf_volume, pts, requires_scale)
+
+    def isosurface(self, level: float = 0.0):
+        """``(vertices [V, 3], faces [F, 3] int32)`` of the surface ``smpl_sdf_volume == level`` in world coordinates
+        (``isosurface.marching_cubes``): node (i, j, k) sits at ``volume_bounds[0] + (i, j, k) * voxel_size``, at the grid NODES (no half
+        voxel, unlike ``isosurface.recon_mesh``).  Faces are wound counter-clockwise seen from outside the body."""
+        if self.smpl_sdf_volume is None:
+            raise ValueError("this WeightVolume was built without an sdf_volume")
+        from . import isosurface
+        return isosurface.marching_cubes(self.smpl_sdf_volume[..., 0], level, spacing=self.voxel_size, origin=self.volume_bounds[0])
 
     def _which(self, volume_type: str) -> torch.Tensor:
         return self.diff_weight_volume if volume_type == "diff" else self.ori_weight_volume
