@@ -1,12 +1,14 @@
 """MI355X-native Animatable Gaussians.  The modules are imported by name (``from animatablegaussians_amd import losses``); the two
-loader-facing functions of ``targets`` are also reachable from the package, resolved on first use so that importing the package stays
-free of side effects."""
+loader-facing functions of ``targets`` and the template stage's ``TemplateField`` are also reachable from the package, resolved on first
+use so that importing the package stays free of side effects."""
 
-__all__ = ["prepare_targets", "boundary_mask"]
+__all__ = ["prepare_targets", "boundary_mask", "TemplateField"]
+
+_HOME = {"prepare_targets": "targets", "boundary_mask": "targets", "TemplateField": "template_field"}
 
 
 def __getattr__(name):
-    if name in __all__:
-        from . import targets
-        return getattr(targets, name)
+    if name in _HOME:
+        import importlib
+        return getattr(importlib.import_module("." + _HOME[name], __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -165,6 +165,18 @@ class AgMeshQueryArgs(ctypes.Structure):      # include/ag_mesh_query.h
                 + [("workspace_bytes", c_sz)])
 
 
+AG_FIELD_MAX_LAYERS = 8
+
+
+class AgFieldLayer(ctypes.Structure):         # include/ag_template_field.h
+    _fields_ = [(n, c_i32) for n in ("K", "width", "act", "concat")]
+
+
+class AgTemplateFieldDesc(ctypes.Structure):  # include/ag_template_field.h
+    _fields_ = ([(n, c_i32) for n in ("multires", "multires_view", "n_geo", "n_color")] + [("softplus_beta", c_f), ("density_b", c_f)]
+                + [("geo", AgFieldLayer * AG_FIELD_MAX_LAYERS), ("color", AgFieldLayer * AG_FIELD_MAX_LAYERS)])
+
+
 # every symbol include/*.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ag_abi_version", ctypes.c_int, []),
@@ -282,6 +294,10 @@ SYMBOLS = [
     ("ag_isosurface_count", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f, c_vp, c_sz, c_vp, c_vp]),
     ("ag_isosurface_emit", ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_vp, c_sz, c_vp, c_i32, c_vp, c_i32,
                                           c_vp]),
+    # include/ag_template_field.h
+    ("ag_template_field_desc_bytes", c_sz, []),
+    ("ag_template_field_blob_floats", c_sz, [ctypes.POINTER(AgTemplateFieldDesc)]),
+    ("ag_template_field_forward", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_targets.h
     ("ag_prepare_targets", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_styleunet.h
