@@ -6,8 +6,9 @@ positional embedding (``utils/embedder.py``), the weight-normalised ``SdfMLP`` a
 the outputs.  ``sdf_grid`` / ``extract_mesh`` are ``TemplateTrainer.test_geometry`` in canonical space (``main_template.py:103-133``): a
 reference template checkpoint becomes the mesh that ``obj_io.save_mesh_ply`` writes as ``template.ply``.
 
-NOT here: the hand fusion (``fuse_hands``), the gradient of the SDF (``compute_grad``, training only), ray sampling and compositing, any
-backward.  Every tensor must be on the GPU; there is no host path and no PyTorch fallback.
+NOT here: the hand fusion (``fuse_hands``), the gradient of the SDF (``compute_grad``, training only), any backward.  Ray sampling and
+compositing, the other half of ``TemplateNet.render``, are ``template_render.py``.  Every tensor must be on the GPU; there is no host path
+and no PyTorch fallback.
 """
 from __future__ import annotations
 
