@@ -274,10 +274,6 @@ __device__ __forceinline__ void sort4(uint64_t (&v)[4])
     cswap(v[1], v[2]);
 }
 
-template <int K> __device__ __forceinline__ void sort_regs(uint64_t (&v)[K]);
-template <> __device__ __forceinline__ void sort_regs<8>(uint64_t (&v)[8]) { sort8(v); }
-template <> __device__ __forceinline__ void sort_regs<4>(uint64_t (&v)[4]) { sort4(v); }
-
 constexpr uint64_t kKeyInf = ~0ull;
 
 // ---- wave-level bitonic network: 64 lanes x 4 keys in registers -> one ascending run of 256 (round 3) ----
@@ -342,9 +338,6 @@ __device__ __forceinline__ void wave_sort256(uint64_t (&v)[4], int lane)
     bitonic_stage<128, 64>(v, lane);
     bitonic_stage<256, 128>(v, lane);
 }
-#ifndef AG_SORT_WAVE_NETWORK
-#define AG_SORT_WAVE_NETWORK 1
-#endif
 constexpr int kSortSmallCap = 2048;   // 512 threads x 4 keys (half the sequential merge steps per round of 256 x 8)
 constexpr int kSortLargeCap = 8192;   // 1024 threads x 8 keys
 
@@ -385,10 +378,9 @@ __device__ __forceinline__ void sort_segment_lds(uint64_t* __restrict__ sk, cons
     const uint32_t base = (uint32_t)tid * (uint32_t)KPT;
 #pragma unroll
     for (int i = 0; i < KPT; i++) v[i] = (base + i < n) ? seg[base + i] : kKeyInf;
-    constexpr bool WAVE_RUNS = !PRESORTED && KPT == 4 && AG_SORT_WAVE_NETWORK;   // runs of 256 from the wave network instead of runs of KPT
-    if constexpr (WAVE_RUNS) {
-        if constexpr (KPT == 4) wave_sort256(v, tid & 63);
-    } else if (!PRESORTED) sort_regs<KPT>(v);
+    constexpr bool WAVE_RUNS = !PRESORTED && KPT == 4;   // runs of 256 from the wave network instead of runs of KPT
+    if constexpr (WAVE_RUNS) wave_sort256(v, tid & 63);
+    else if constexpr (!PRESORTED) sort8(v);
     if (base < n) {
 #pragma unroll
         for (int i = 0; i < KPT; i++) bufA[base + i] = v[i];

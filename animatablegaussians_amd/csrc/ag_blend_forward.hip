@@ -29,7 +29,6 @@
 // travels with the record.  Results differ from a serial evaluation only by the association of the transmittance
 // product (a few ulp).
 // Bound: VALU + LDS; HBM traffic is the compulsory 52 B/instance (x8 regions, served by L2) + 24 B/pixel.
-#include <cstdlib>
 #include "ag_common.h"
 
 namespace ag {
@@ -47,15 +46,6 @@ struct BlendFwdParams {
     float* __restrict__ out_alpha;
     uint32_t* __restrict__ n_contrib;
 };
-
-#define AG_ROW_SHR(n) (0x110 + (n))
-
-template <int N>
-__device__ __forceinline__ float row_shr(float v, float fill)
-{
-    // lane l of each 16-lane row receives lane l-N of the same row; the first N lanes receive `fill`
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), AG_ROW_SHR(N), 0xf, 0xf, false));
-}
 
 __device__ __forceinline__ float row_lane15(float v)   // row_newbcast:15: every lane receives lane 15 of its 16-lane row
 {
@@ -79,20 +69,6 @@ __device__ __forceinline__ float row_inclusive_product(float x)
     return x;
 }
 
-__device__ __forceinline__ float row_total(float x)   // sum over the row, valid in lane 15 of the row
-{
-    x += row_shr<1>(x, 0.0f);
-    x += row_shr<2>(x, 0.0f);
-    x += row_shr<4>(x, 0.0f);
-    x += row_shr<8>(x, 0.0f);
-    return x;
-}
-
-__device__ __forceinline__ float row_read(float v, int lane, int k)   // value of lane k of this lane's row
-{
-    return __shfl(v, (lane & 48) + k, 64);
-}
-
 // AG_FWD_STATS (diagnostic build only: profiles/ub/build_variant.sh fstats ag_blend_forward -DAG_FWD_STATS, profiles/fwd_step_stats.py): lane 0 of
 // every wave adds its work figures to global counters.  Not compiled into the product.
 #ifdef AG_FWD_STATS
@@ -111,36 +87,16 @@ extern "C" int ag_debug_fwd_stats(unsigned long long* out)
 #define FST(k, v) do { } while (0)
 #endif
 
-#ifndef AG_FWD_PRIO
-#define AG_FWD_PRIO 0
-#endif
-#ifndef AG_FWD_PRIO_T1
-#define AG_FWD_PRIO_T1 1024u
-#define AG_FWD_PRIO_T2 2048u
-#define AG_FWD_PRIO_T3 4096u
-#endif
-#ifndef AG_FWD_LDS_PAD
-#define AG_FWD_LDS_PAD 0
-#endif
 #ifndef AG_FWD_WAVES_PER_SIMD
 #define AG_FWD_WAVES_PER_SIMD 8      // <= 64 VGPRs: four resident workgroups per CU (71 VGPRs without the bound: 58.8 us against 52.2, profiles/ab_fwd.sh)
 #endif
-#if AG_FWD_WAVES_PER_SIMD
 __global__ void __launch_bounds__(kBlendThreads, AG_FWD_WAVES_PER_SIMD) blend_forward_kernel(BlendFwdParams p)
-#else
-__global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdParams p)
-#endif
 {
     constexpr int NW = kBlendThreads / 64;
     __shared__ float4 s_rec[kChunk * 3];
     __shared__ int s_wave_cnt[2][NW];
     __shared__ int s_wave_done[NW];
     __shared__ uint16_t s_widx[NW][kChunk];   // per wave: the compacted entries that can reach ITS 2x2 pixels, in list order
-#if AG_FWD_LDS_PAD          /* diagnostic: fewer resident workgroups per CU (profiles/r03_bwd_step_stats.txt: the forward's time against occupancy) */
-    __shared__ uint32_t s_pad[AG_FWD_LDS_PAD / 4];
-    if (threadIdx.x == 0 && blockIdx.x == 0xffffffffu) s_pad[0] = 1u;
-    asm volatile("" :: "v"(s_pad[threadIdx.x & 7]));
-#endif
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int row = lane >> 4, e = lane & 15;
@@ -163,7 +119,7 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
     }
 
     // Static work assignment (see ItemIter); the descriptor of item i+1 is fetched while item i is blended.
-    ItemIter it(blockIdx.x, gridDim.x, n_active);
+    ItemIter<kRegionsPerTile> it(blockIdx.x, gridDim.x, n_active);
     uint32_t tr, rg;
     bool have = it.next(tr, rg);
     uint4 hdr = make_uint4(0u, 0u, 0u, 0u);
@@ -177,15 +133,6 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
 
         const int tile = (int)hdr.x, reg = (int)hdr.w;
         const uint2 range = make_uint2(hdr.y, hdr.z);
-#if AG_FWD_PRIO
-        {   // issue priority by list length (the regions of the longest tiles are the kernel's critical path)
-            const uint32_t len = range.y - range.x;
-            if (len >= AG_FWD_PRIO_T3) __builtin_amdgcn_s_setprio(3);
-            else if (len >= AG_FWD_PRIO_T2) __builtin_amdgcn_s_setprio(2);
-            else if (len >= AG_FWD_PRIO_T1) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
         const int tile_x = tile % p.gx, tile_y = tile / p.gx;
         const int rx0 = tile_x * kTileX + (reg & 1) * kRegW, ry0 = tile_y * kTileY + (reg >> 1) * kRegH;
         // the wave's 4 pixels form a 2x2 block (better coherence of the per-wave early-outs than a 4x1 strip)
@@ -212,24 +159,14 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
             const float4* src = reinterpret_cast<const float4*>(p.rec + id0);
             r0 = src[0]; r1 = src[1]; r2 = src[2];
         }
-        // cull of chunk 0
+        // cull of chunk 0: the cut-off disc.  (The backward's exact quadratic-form cull was measured here and NOT kept: fewer survivors,
+        // 62.3 us against 47.2 -- profiles/r06_fwd_exact_cull.txt.)
         bool keep;
-#ifndef AG_FWD_TIGHT_CULL
-#define AG_FWD_TIGHT_CULL 0      /* round 6, measured and NOT kept: the exact quadratic-form cull of the backward (rect_reaches) instead of the cut-off
-                                    disc keeps 172 instead of 196 entries per region and 58 instead of 72 per wave (2.9 instead of 3.4 steps), all raster
-                                    tests pass -- and the kernel takes 62.3 us instead of 47.2 (74.7 with the short-circuit form): this kernel is bound by
-                                    its per-item critical path, and the test's ~15 dependent instructions per cull pass sit on it while the steps it
-                                    saves do not pay them back (profiles/r06_fwd_exact_cull.txt).  -DAG_FWD_TIGHT_CULL=1 builds it. */
-#endif
-#if AG_FWD_TIGHT_CULL
-        keep = (int)(range.x + tid < range.y) & (int)rect_reaches(qx0f - r0.x, qx1f - r0.x, qy0f - r0.y, qy1f - r0.y, r0.z, r0.w, r1.x, r2.w);     // no short circuit: a branch here waits for the prefetched records on the spot
-#else
         {
             const float ddx = fmaxf(fmaxf(qx0f - r0.x, r0.x - qx1f), 0.f);
             const float ddy = fmaxf(fmaxf(qy0f - r0.y, r0.y - qy1f), 0.f);
             keep = (range.x + tid < range.y) && ((ddx * ddx + ddy * ddy) <= r2.z);
         }
-#endif
         unsigned long long mask = __ballot(keep);
         if (lane == 0) { s_wave_cnt[0][wave] = __popcll(mask); s_wave_done[wave] = 0; }
         lds_barrier();
@@ -248,9 +185,9 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
                 static_assert(NW == 8, "the prefix below covers 8 waves");
                 const int c = s_wave_cnt[cpar][lane & 7];
                 int x = c;
-                x += __builtin_amdgcn_update_dpp(0, x, AG_ROW_SHR(1), 0xf, 0xf, true);
-                x += __builtin_amdgcn_update_dpp(0, x, AG_ROW_SHR(2), 0xf, 0xf, true);
-                x += __builtin_amdgcn_update_dpp(0, x, AG_ROW_SHR(4), 0xf, 0xf, true);      // lanes 0..7: inclusive prefix
+                x += __builtin_amdgcn_update_dpp(0, x, AG_DPP_ROW_SHR(1), 0xf, 0xf, true);
+                x += __builtin_amdgcn_update_dpp(0, x, AG_DPP_ROW_SHR(2), 0xf, 0xf, true);
+                x += __builtin_amdgcn_update_dpp(0, x, AG_DPP_ROW_SHR(4), 0xf, 0xf, true);      // lanes 0..7: inclusive prefix
                 const int wv = __builtin_amdgcn_readfirstlane(wave);
                 off = __builtin_amdgcn_readlane(x, wv) - __builtin_amdgcn_readlane(c, wv);
                 K = __builtin_amdgcn_readlane(x, 7);
@@ -259,7 +196,7 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
                 const int slot = off + rank;
                 s_rec[slot * 3 + 0] = r0;
                 s_rec[slot * 3 + 1] = r1;
-                s_rec[slot * 3 + 2] = make_float4(r2.x, r2.y, __uint_as_float(k - range.x + 1u), AG_FWD_TIGHT_CULL ? r2.w : r2.z);  // b, depth, 1-based position, qcut (r2cut)
+                s_rec[slot * 3 + 2] = make_float4(r2.x, r2.y, __uint_as_float(k - range.x + 1u), r2.z);  // b, depth, 1-based position, r2cut
             }
             // issue the gathers of chunk c+1 and the index loads of chunk c+2; both are consumed after the blend
             const uint32_t kn = k + kChunk, knn = kn + kChunk;
@@ -274,15 +211,7 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
             // Each wave keeps the indices of the entries whose cut-off disc touches ITS block (same conservative test, so the
             // dropped entries contribute exactly nothing) and blends only those: half the steps of walking the region's list.
             int cntw = 0;
-#if defined(AG_FWD_KO) && AG_FWD_KO == 1      /* timing probe (same results, more steps): no second cull -- every wave walks all K region survivors */
-            if (!__all(done)) {
-                for (int i0 = 0; i0 < K; i0 += 64) if (i0 + lane < K) s_widx[wave][i0 + lane] = (uint16_t)(i0 + lane);
-                cntw = K;
-            }
-            if (false) {
-#else
             if (!__all(done)) {     // a wave whose four pixels are finished has nothing to pick from this chunk
-#endif
                 const float bx0 = (float)(rx0 + (wave & 3) * 2), by0 = (float)(ry0 + (wave >> 2) * 2);
                 for (int i0 = 0; i0 < K; i0 += 64) {
                     const int i = i0 + lane;
@@ -290,14 +219,9 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
                     if (i < K) {
                         const float4 a0 = s_rec[i * 3 + 0];
                         const float r2c = s_rec[i * 3 + 2].w;
-#if AG_FWD_TIGHT_CULL
-                        const float cc0 = s_rec[i * 3 + 1].x;
-                        mine = rect_reaches(bx0 - a0.x, bx0 + 1.0f - a0.x, by0 - a0.y, by0 + 1.0f - a0.y, a0.z, a0.w, cc0, r2c);
-#else
                         const float ddx = fmaxf(fmaxf(bx0 - a0.x, a0.x - (bx0 + 1.0f)), 0.f);
                         const float ddy = fmaxf(fmaxf(by0 - a0.y, a0.y - (by0 + 1.0f)), 0.f);
                         mine = (ddx * ddx + ddy * ddy) <= r2c;
-#endif
                     }
                     const unsigned long long m = __ballot(mine);
                     if (mine) s_widx[wave][cntw + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)i;
@@ -308,9 +232,6 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
             if (wave == 0) FST(FS_REGION_SURV, K);
             FST(FS_SUBCULL_PASSES, (K + 63) / 64); FST(FS_WAVE_SURV, cntw);
             // ---- blend: 16 entries per step per pixel row ----
-#if defined(AG_FWD_KO) && AG_FWD_KO == 2      /* timing probe (wrong results): the culls alone, no blend steps */
-            cntw = 0;
-#endif
             for (int s0 = 0; s0 < cntw; s0 += 16) {
                 if (__all(done)) { FST(FS_BREAKS, 1); break; }
                 FST(FS_STEPS, 1);
@@ -363,15 +284,11 @@ __global__ void __launch_bounds__(kBlendThreads) blend_forward_kernel(BlendFwdPa
             }
 
             // ---- cull of the next chunk (its records have landed by now) + completion vote ----
-#if AG_FWD_TIGHT_CULL
-            keep = (int)(kn < range.y) & (int)rect_reaches(qx0f - r0.x, qx1f - r0.x, qy0f - r0.y, qy1f - r0.y, r0.z, r0.w, r1.x, r2.w);
-#else
             {
                 const float ddx = fmaxf(fmaxf(qx0f - r0.x, r0.x - qx1f), 0.f);
                 const float ddy = fmaxf(fmaxf(qy0f - r0.y, r0.y - qy1f), 0.f);
                 keep = (kn < range.y) && ((ddx * ddx + ddy * ddy) <= r2.z);
             }
-#endif
             mask = __ballot(keep);
             const int wdone = __all(done);
             if (lane == 0) { s_wave_cnt[cpar ^ 1][wave] = __popcll(mask); s_wave_done[wave] = wdone; }

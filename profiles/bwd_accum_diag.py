@@ -1,5 +1,6 @@
 """Worst blend-backward accumulator elements of BASELINE configs[4] (1.07 M Gaussians @2048^2) against the fp64 oracle, per slot, with the
-error percentiles: run once per kernel variant (AG_BWD_KERNEL=0|1) to compare their error statistics (r03: identical)."""
+error percentiles: run once per build of the library (AG_LIB_PATH) to compare their error statistics (r03, region against wave kernel:
+identical).  The first dL_dmeans2D column is saved as m2x.npy under $AB_OUT (default: build/, as profiles/ab_bwd.sh)."""
 import os, sys
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -29,5 +30,6 @@ for name, slots in h._SLOT_OF.items():
         q = np.percentile(ratio, [50, 99, 99.99])
         print(f"{name}[{col}]: worst ratio {ratio[i]:.3f} at {i}: got {g[i]:.6e} ref {r[i]:.6e} abs_sum {acc_ref['abs_sum'][i, slot]:.4e}; ratio pct 50/99/99.99 {q[0]:.4f} {q[1]:.4f} {q[2]:.4f}; mean|d|/(eps*abs_sum) {np.mean(np.abs(g-r)/(eps*acc_ref['abs_sum'][:,slot]+1e-30)):.3f}")
         if name == "dL_dmeans2D" and col == 0:
-            np.save(os.path.join(ROOT, "gpurun_out", f"m2x_{os.environ.get('AG_BWD_KERNEL','0')}.npy"), g.astype(np.float32))
+            out_dir = os.environ.get("AB_OUT", os.path.join(ROOT, "build")); os.makedirs(out_dir, exist_ok=True)
+            np.save(os.path.join(out_dir, "m2x.npy"), g.astype(np.float32))
             print("   tiles_touched", ref["tiles_touched"][i], "radius", ref["radii"][i], "opacity", ref["conic_opacity"][i], "means2D", ref["means2D"][i])
