@@ -154,7 +154,6 @@ struct GatherProblem {
     float slope, act_scale;
     PtrTable noise_t;      // act 1: per-instance noise [OHf * OWf] (null: no noise); act 2: per-instance addend [M][OHf * OWf]
     PtrTable nw_t;         // act 1: per-instance noise weight [1]
-    int xcd_order;         // 1: workgroups take their (N tile, instance * M tile) in the XCD-aware order of tile_of_workgroup() (host: gridDim.x * gridDim.y % 8 == 0)
     float* out_amax;       // act != 0: zeroed [G][kAmaxParts] slots for the largest magnitude of the activated output (ConvAct::out_amax), or null
     int* status;           // host-visible sticky flag raised on a non-finite accumulator (ag_conv_status), or null
     int status_tag;        // what the offending launch stores there: kind << 28 | rows << 14 | channels (status_tag_of)
@@ -176,23 +175,6 @@ struct GroupView {
     const float* noise;          // activation operands of the instance (GatherProblem::act)
     float nw;
 };
-// XCD-aware order (round 4).  The hardware deals workgroups to the 8 XCDs round-robin by linear id, so neighbouring N tiles -- neighbouring
-// image rows, whose 3 x 3 gathers read the same input rows -- and the M tiles of one N tile (which gather the SAME input) landed on eight
-// different L2s: PMC on a 256 -> 256 layer at 256^2 showed 523 MB fetched by L2 per launch for 69.5 MB of unique input
-// (profiles/r04_pmc_traffic_gather_conv_f16_256_256_256.txt).  Here XCD j takes the j-th eighth of the (N tile, instance x M tile) pairs,
-// M tiles and instances of one N tile back to back, N tiles in image order.
-struct TileId { int bx, by; };
-__device__ __forceinline__ TileId tile_of_workgroup(const GatherProblem& p)
-{
-    TileId t{ (int)blockIdx.x, (int)blockIdx.y };
-    if (p.xcd_order) {
-        const int L = (int)blockIdx.x + (int)gridDim.x * (int)blockIdx.y;
-        const int Lg = (L & 7) * (((int)gridDim.x * (int)gridDim.y) >> 3) + (L >> 3);
-        t.bx = Lg / (int)gridDim.y;
-        t.by = Lg - t.bx * (int)gridDim.y;
-    }
-    return t;
-}
 __device__ __forceinline__ GroupView group_view(const GatherProblem& p, int by)
 {
     GroupView v;
@@ -324,16 +306,16 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
     const int wm = wave / WVN, wn = wave % WVN;
 
     // class of this workgroup (wave-uniform)
-    const TileId tw = tile_of_workgroup(p);
+    const int bx = blockIdx.x, by = blockIdx.y;
     int ci = 0;
 #pragma unroll
     for (int c = 1; c < kMaxClasses; c++)
-        if (c < p.nclasses && tw.bx >= p.cls[c].tile_begin) ci = c;
+        if (c < p.nclasses && bx >= p.cls[c].tile_begin) ci = c;
     const GatherClass& cl = p.cls[ci];
     const int gw = cl.gw, ntaps = cl.ntaps;
     const int N = cl.gh * gw;
-    const GroupView gv = group_view(p, tw.by);
-    const int m0 = gv.my * BM, n0 = (tw.bx - cl.tile_begin) * BN;
+    const GroupView gv = group_view(p, by);
+    const int m0 = gv.my * BM, n0 = (bx - cl.tile_begin) * BN;
 
     const int n_loc = tid % BN, g = (wave * 64) / BN;   // g is wave-uniform (BN >= 64)
     const int n = n0 + n_loc;
@@ -727,16 +709,16 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WVN, wn = wave % WVN;
 
-    const TileId tw = tile_of_workgroup(p);
+    const int bx = blockIdx.x, by = blockIdx.y;
     int ci = 0;
 #pragma unroll
     for (int c = 1; c < kMaxClasses; c++)
-        if (c < p.nclasses && tw.bx >= p.cls[c].tile_begin) ci = c;
+        if (c < p.nclasses && bx >= p.cls[c].tile_begin) ci = c;
     const GatherClass& cl = p.cls[ci];
     const int gw = cl.gw, ntaps = cl.ntaps;
     const int N = cl.gh * gw;
-    const GroupView gv = group_view(p, tw.by);
-    const int m0 = gv.my * BM, n0 = (tw.bx - cl.tile_begin) * BN;
+    const GroupView gv = group_view(p, by);
+    const int m0 = gv.my * BM, n0 = (bx - cl.tile_begin) * BN;
 
     const int n_loc = tid % BN, g = (wave * 64) / BN;
     const int n = n0 + n_loc;
@@ -889,179 +871,6 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
         }
     }
     if constexpr (F16) unscale_f16<WMB, WNB>(acc, sa.inv, sb.inv);
-    gather_epilogue<WMB, WNB>(p, gv, cl, acc, m0, n0, N, wm, wn, lane);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Round 6: the same GEMM with an LDS-DMA loader over PRE-SPLIT activation planes
-// ------------------------------------------------------------------------------------------------------------------
-// gather_conv_split_kernel converts every gathered activation fp32 -> (hi, lo) fp16 in the loader thread, once per TAP and per OUTPUT-CHANNEL
-// TILE that reads it (18 times on a 256 -> 256 layer), through VGPRs: 8 scalar global loads, ~40 VALU and the LDS stores per thread and
-// 16-deep K tile -- as much issue time as the tile's MFMAs, serial with them inside a wave (PMC, profiles/r05_pmc_conv_modes: matrix pipe
-// 48 % busy).  Here the split happens ONCE per launch, in a streaming pass of its own (presplit_kernel: fp32 [C][H][W] -> fp16 planes
-// [plane][C / 8][H W][8], 4 bytes per element like the fp32 tensor), and a K tile's operands reach LDS by global_load_lds_dwordx4: a lane's
-// 16-byte chunk = 8 consecutive channels of ONE pixel of one plane, so the lane-linear LDS image of a DMA (lane i -> base + 16 i) is the
-// swizzled [row][chunk] layout read_split_operands wants once the lane picks the matching (row, chunk) as its SOURCE; a tap that falls
-// outside the image, or a row past the class, reads a 64-byte zero page instead (the source address is per lane, so padding costs two
-// selects).  No staging registers, no conversion, no LDS stores; per K tile a wave issues its DMAs (one per 1-KB piece: a 32-row slice of
-// an activation plane, or 1 KB of the packed weight tile, which already is its LDS image) and twelve MFMAs on a 64 x 64 wave tile.  Three
-// LDS buffers, DMAs two tiles ahead, one barrier per tile: wait vmcnt(own DMAs of ONE tile) -> barrier -> issue tile kt + 2 -> read -> MFMA.
-__device__ __attribute__((aligned(64))) uint32_t g_zero_page[16];
-
-struct PresplitProblem {
-    const float* x;            // [G'][C][HW]
-    char* xs;                  // [G'][planes][Cpad / 8][HW][8] fp16
-    const float* amax;         // [G' or 1][kAmaxParts]
-    long long x_gs;            // floats between instances (0: one shared instance)
-    long long xs_gs;           // bytes between instances of xs
-    int C, Cpad, HW, planes;
-};
-__global__ void __launch_bounds__(256) presplit_kernel(PresplitProblem p)
-{
-    const int grp = blockIdx.z, cb = blockIdx.y;
-    const TensorScale sc = tensor_scale(p.amax + (p.x_gs ? (size_t)grp * kAmaxParts : 0), 1.f, threadIdx.x & 63);
-    const float* __restrict__ x = p.x + (size_t)grp * p.x_gs;
-    char* __restrict__ xs = p.xs + (size_t)grp * p.xs_gs;
-    const size_t plane_b = (size_t)(p.Cpad / 8) * p.HW * 16;
-    for (int q = blockIdx.x * 256 + threadIdx.x; q < p.HW; q += gridDim.x * 256) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int c = cb * 8 + j;
-            v[j] = c < p.C ? x[(size_t)c * p.HW + q] * sc.s : 0.f;
-        }
-        u32x4 h, l;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            uint32_t a, b;
-            split_pair_h(v[2 * e], v[2 * e + 1], a, b);
-            h[e] = a; l[e] = b;
-        }
-        const size_t off = ((size_t)cb * p.HW + q) * 16;
-        *reinterpret_cast<u32x4*>(xs + off) = h;
-        if (p.planes == 2) *reinterpret_cast<u32x4*>(xs + plane_b + off) = l;
-    }
-}
-
-// waves per SIMD the register budget is cut for: one 8-wave workgroup per CU for the 128 x 64 wave tiles (128 accumulator registers), two for the
-// 64 x 64 ones, three 4-wave workgroups
-constexpr int dma_wps(int wmb, int wnb, int nt) { return wmb * wnb > 4 ? 2 : (nt == 512 ? 4 : 3); }
-template <int WMB, int WNB, int WVM, int WVN, int NTERMS>
-__global__ void __launch_bounds__(64 * WVM * WVN, dma_wps(WMB, WNB, 64 * WVM * WVN)) gather_conv_dma_kernel(GatherProblem p, const char* __restrict__ xs, long long xs_gs)
-{
-    constexpr int NPL = planes_of(NTERMS);
-    static_assert(is_f16_form(NTERMS), "the DMA loader serves the fp16 forms");
-    using T = SplitTile<WMB, WNB, WVM, WVN, NPL>;
-    constexpr int BM = T::BM, BN = T::BN, NT = T::NT, NW = NT / 64;
-    constexpr int PA = T::a_bytes / 1024, PB = T::b_bytes / 1024;      // 1-KB pieces of a K tile's two operand images
-    static_assert((PA + PB) % NW == 0, "every wave issues the same number of DMAs per tile (the vmcnt count is an immediate)");
-    static_assert(PA % NW == 0, "piece k of every wave is on the same side (A or B): no branch per piece");
-    constexpr int PER = (PA + PB) / NW;
-    constexpr int NBUF = 3;
-    constexpr int stage_bytes = T::a_bytes + T::b_bytes;
-    __shared__ __attribute__((aligned(1024))) char smem[NBUF * stage_bytes];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WVN, wn = wave % WVN;
-
-    const TileId tw = tile_of_workgroup(p);
-    int ci = 0;
-#pragma unroll
-    for (int c = 1; c < kMaxClasses; c++)
-        if (c < p.nclasses && tw.bx >= p.cls[c].tile_begin) ci = c;
-    const GatherClass& cl = p.cls[ci];
-    const int gw = cl.gw, ntaps = cl.ntaps;
-    const int N = cl.gh * gw;
-    const GroupView gv = group_view(p, tw.by);
-    const int m0 = gv.my * BM, n0 = (tw.bx - cl.tile_begin) * BN;
-    const int HW = p.Hg * p.Wg;
-
-    f32x16 acc[WMB][WNB];
-#pragma unroll
-    for (int i = 0; i < WMB; i++)
-#pragma unroll
-        for (int j = 0; j < WNB; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
-
-    const int nkt_all = cl.nkt;
-    const int kt_beg = min(nkt_all, (int)blockIdx.z * p.kt_per_split), kt_end = min(nkt_all, kt_beg + p.kt_per_split);
-    const int nkt = kt_end - kt_beg;
-    TensorScale sa = tensor_scale(p.amax_a + (size_t)gv.grp * kAmaxParts, p.amax_a_mult, lane);
-    TensorScale sb = tensor_scale(p.amax_b + (p.x_gs ? (size_t)gv.grp * kAmaxParts : 0), 1.f, lane);
-
-    // ---- this wave's pieces.  Piece q < PA: bytes [1024 q, 1024 q + 1024) of the packed weight tile; piece PA + j: plane j / (BN / 32), rows
-    //      32 (j % (BN / 32)) ... + 31 of the activation tile; lane i of a B piece owns LDS chunk i = (row i / 2, slot i & 1), slot = kh ^ bit 3 of row
-    const char* const a_tile0 = reinterpret_cast<const char*>(p.At) + ((size_t)gv.grp * p.at_gs + (size_t)cl.at_off) * (2 * NPL) + ((size_t)gv.my * nkt_all + kt_beg) * T::a_bytes;
-    const char* const xs_g = xs + (size_t)(p.x_gs ? gv.grp : 0) * xs_gs;
-    const size_t plane_b = (size_t)(p.Cpad / 8) * HW * 16;
-    const char* src[PER];          // per-lane source of piece k at tile 0 / tap offset 0 / channel block 0
-    uint32_t vmask[PER];           // B pieces: taps of this lane's pixel that lie inside the image; A pieces: all ones
-#pragma unroll
-    for (int k = 0; k < PER; k++) {
-        const int q = wave + k * NW;                       // wave-uniform
-        if (k * NW < PA) {
-            src[k] = a_tile0 + q * 1024 + lane * 16;
-            vmask[k] = 0xffffffffu;
-        } else {
-            const int j = q - PA, pl = j / (BN / 32), rp = j % (BN / 32);
-            const int row = rp * 32 + (lane >> 1), kh = (lane & 1) ^ ((row >> 3) & 1);
-            const int n = n0 + row;
-            const bool n_ok = n < N;
-            const int gy = n_ok ? n / gw : 0, gx = n_ok ? n - (n / gw) * gw : 0;
-            const int iy0 = gy * p.sy, ix0 = gx * p.sx;
-            uint32_t vm = 0;
-            for (int t = 0; t < ntaps; t++) {
-                const int iy = iy0 + cl.dy[t], ix = ix0 + cl.dx[t];
-                if (n_ok && iy >= 0 && iy < p.Hg && ix >= 0 && ix < p.Wg) vm |= 1u << t;
-            }
-            vmask[k] = vm;
-            src[k] = xs_g + (size_t)pl * plane_b + ((long long)kh * HW + (long long)iy0 * p.Wg + ix0) * 16;
-        }
-    }
-    const int tl = lane & (kMaxTaps - 1);
-    const int toff_vec = cl.dy[tl] * p.Wg + cl.dx[tl];
-    const char* const zero = reinterpret_cast<const char*>(g_zero_page) + (lane & 3) * 16;
-
-    int t_cur = kt_beg % ntaps;
-    long long cb_off = (long long)(kt_beg / ntaps) * 2 * HW * 16;      // byte offset of the tile's channel-block pair inside a plane
-    long long a_off = 0;
-    auto issue = [&](int buf) {
-        char* const stage = smem + buf * stage_bytes;
-        const long long uoff = cb_off + (long long)__builtin_amdgcn_readlane(toff_vec, t_cur) * 16;
-#pragma unroll
-        for (int k = 0; k < PER; k++) {
-            const int q = wave + k * NW;
-            const char* g;
-            if (k * NW < PA) g = src[k] + a_off;
-            else          g = ((vmask[k] >> t_cur) & 1u) ? src[k] + uoff : zero;
-            char* dst = stage + q * 1024;                  // A pieces first, then the B planes: the stage IS [a image][b image]
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-        }
-        a_off += T::a_bytes;
-        t_cur++;
-        const bool wrap = t_cur == ntaps;
-        t_cur = wrap ? 0 : t_cur;
-        cb_off += wrap ? (long long)2 * HW * 16 : 0;
-    };
-    SplitOperands<WMB, WNB> O;
-
-    if (nkt > 0) {
-        issue(0);
-        if (nkt > 1) issue(1);
-        int buf = 0;
-        for (int kt = 0; kt < nkt; kt++) {
-            if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER) : "memory");
-            else              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            lds_barrier();
-            if (kt + 2 < nkt) issue(buf >= 1 ? buf - 1 : NBUF - 1);          // (kt + 2) % 3
-            const char* stage = smem + buf * stage_bytes;
-            read_split_operands<WMB, WNB, BM, BN, NTERMS>(stage, stage + T::a_bytes, wm, wn, lane, O);
-            mma_split_h<WMB, WNB, NTERMS>(O, acc);
-            buf = buf + 1 == NBUF ? 0 : buf + 1;
-        }
-    }
-    unscale_f16<WMB, WNB>(acc, sa.inv, sb.inv);
     gather_epilogue<WMB, WNB>(p, gv, cl, acc, m0, n0, N, wm, wn, lane);
 }
 
@@ -1779,52 +1588,6 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_
     wgrad_store<WMB, WNB>(p, acc, F16 ? sa.inv * sb.inv : 1.f, grp, c_g, m0, n0, Nw, wm, wn, lane);
 }
 
-// Matrix-pipe calibration: every wave issues `iters` x 4 independent v_mfma_f32_32x32x2_f32 back to back, no memory.
-// Used by profiles/mfma_peak.py to measure the attainable fp32 MFMA rate of the box the convolutions are priced against.
-__global__ void __launch_bounds__(256) mfma_rate_kernel(int iters, float* out)
-{
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[i][r] = 0.f;
-    float a = 1.0f + threadIdx.x * 1e-6f, b = 0.5f;
-    for (int it = 0; it < iters; it++) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[i], 0, 0, 0);
-    }
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) v += acc[i][r];
-    if (v == 12345.678f) out[0] = v;     // keep the chain alive
-}
-
-// The same for v_mfma_f32_32x32x16_bf16 (fp32 accumulation): the rate a three-term bf16 split of the fp32 operands
-// (a_hi b_hi + a_hi b_lo + a_lo b_hi) would run on -- calibration only, nothing in the product uses it.
-__global__ void __launch_bounds__(256) mfma_rate_bf16_kernel(int iters, float* out)
-{
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[i][r] = 0.f;
-    bf16x8 a, b;
-#pragma unroll
-    for (int i = 0; i < 8; i++) { a[i] = (__bf16)(1.0f + (threadIdx.x & 7) * 0.125f); b[i] = (__bf16)0.5f; }
-    for (int it = 0; it < iters; it++) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i], 0, 0, 0);
-    }
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) v += acc[i][r];
-    if (v == 12345.678f) out[0] = v;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
@@ -1862,8 +1625,7 @@ int conv_absmax(const AmaxTensor* t, int n, int G, float* out, hipStream_t s, fl
             // kAmaxParts -- 256 x jobs workgroups of 1024 threads for a stack of 36 K-float weight tensors were mostly dispatch
             long long largest = 0;
             for (int j = 0; j < jobs; j++) largest = std::max(largest, J.len[j] * J.rows[j]);
-            static const bool sized = [] { const char* e = getenv("AG_AMAX_SIZED_GRID"); return !(e && e[0] == '0'); }();
-            const int parts = sized ? (int)std::min<long long>(kAmaxParts, std::max<long long>(1, (largest + 16383) / 16384)) : kAmaxParts;
+            const int parts = (int)std::min<long long>(kAmaxParts, std::max<long long>(1, (largest + 16383) / 16384));
             hipLaunchKernelGGL(absmax_kernel, dim3(parts, jobs), dim3(kAmaxThreads), 0, s, J);
         }
         jobs = 0;
@@ -1993,39 +1755,16 @@ static int choose_splits(long long tiles, int Mpad, int Ncols, int nkt, int G = 
     return best;
 }
 
-// Round 6 EXPERIMENT (opt-in, AG_CONV_DMA=1: big tiles only, =2: every eligible launch): the LDS-DMA loader over pre-split planes
-// (gather_conv_dma_kernel) for the fp16 forms on whole 16-channel blocks.  Correct (tests/test_conv_gpu.py green in this mode) and NOT faster on the
-// training step: profiles/r06_conv_dma.md.
-static bool conv_dma_possible(int Cg)
-{
-    static const bool dma_on = [] { const char* e = getenv("AG_CONV_DMA"); return e && (e[0] == '1' || e[0] == '2'); }();      // OPT-IN: measured no net gain (below)
-    return dma_on && is_f16_form(split_terms()) && Cg % BK == 0;
-}
-// Workgroup tile.  A 128 x 128 tile moves 16 KB of operands per 16-deep K tile from L2 for 1.57 M products: 96 products per byte, i.e. ~26 TB/s of
-// L2 -> LDS traffic at the matrix pipe's peak -- the 128-wide kernels are L2-bandwidth-bound at about half of it (profiles/r06_conv_dma.md).  With the
-// DMA loader's registers free for accumulators: 256 x 256 (192 products per byte) where the output has whole 256-row tiles and enough of them to
-// fill the chip, 128 x 256 (131) for the 128-channel layers; AG_CONV_BIG_TILES=0 keeps the 128-wide tiles.
-static void pick_tile(int M, long long N, int G, bool dma, int& bm, int& bn)
-{
-    bm = pick_bm(M); bn = bn_of(bm);
-    static const bool big = [] { const char* e = getenv("AG_CONV_BIG_TILES"); return !(e && e[0] == '0'); }();
-    if (!dma || !big) return;
-    const int terms = split_terms();
-    const long long nt256 = (N + 255) / 256;
-    if (M % 256 == 0 && nt256 * (M / 256) * G >= 192) { bm = 256; bn = 256; }
-    else if (M % 128 == 0 && terms == kF16 && nt256 * (M / 128) * G >= 384) { bm = 128; bn = 256; }
-}
-
 // Fills tile_begin / col_begin / at_off / nkt of the classes (dy, dx, gh, gw, y0, x0, ntaps set by the caller), packs the
 // weights of all classes with one launch and runs them with one launch (+ one split-K finish).
 static int pack_and_launch(GatherProblem& gp, const TapSet* taps, int bm, const PtrTable& w, long long stride_c, long long stride_m,
                            float wscale, int k, float* At, float* partial, float* amax, const AmaxTensor& w_shape, const float* pre_w,
-                           const float* pre_in, hipStream_t s, bool skip_pack = false, char* xs_buf = nullptr, int bn = 0)
+                           const float* pre_in, hipStream_t s, bool skip_pack = false)
 {
     const bool split = split_math();
     const int terms = split_terms();
     const bool f16 = is_f16_form(terms);
-    const int BN = bn ? bn : bn_of(bm);
+    const int BN = bn_of(bm);
     const int G = gp.G;
     PackProblem pp;
     pp.w_t = w; pp.At = At; pp.C = gp.Cg; pp.Cpad = gp.Cpad; pp.M = gp.M; pp.Mpad = gp.Mpad; pp.BM = bm; pp.nclasses = gp.nclasses;
@@ -2089,50 +1828,12 @@ static int pack_and_launch(GatherProblem& gp, const TapSet* taps, int bm, const 
     gp.part_gs = (long long)splits * gp.Mpad * cols;
     gp.At = At;
     dim3 grid((unsigned)tiles, (gp.Mpad / bm) * G, splits);
-    // XCD-aware tile order (tile_of_workgroup), opt-in with AG_CONV_XCD=1: 4.2x less L2-miss traffic (PMC: 524 -> 124 MB per launch on a
-    // 256 -> 256 layer at 256^2) and no time gained (ABBA same-box: 33.37 vs 33.45 ms per step) -- the kernel does not wait for those misses
-    // (profiles/r04_conv_xcd_order_ab.txt).  Needs whole eighths.
-    static const bool xcd_on = [] { const char* e = getenv("AG_CONV_XCD"); return e && e[0] == '1'; }();
-    gp.xcd_order = (xcd_on && ((long long)grid.x * grid.y) % 8 == 0 && (long long)grid.x * grid.y >= 64) ? 1 : 0;
     double flops = 0.0;
     for (int c = 0; c < gp.nclasses; c++)
         if (!gp.cls[c].zero_weights) flops += 2.0 * G * gp.M * (double)gp.cls[c].gh * gp.cls[c].gw * gp.cls[c].ntaps * gp.Cg;
     char tag[64];
     snprintf(tag, sizeof(tag), "g bm%d G%d M%d C%d N%d cls%d nkt%d sp%d wg%lld", bm, G, gp.M, gp.Cg, cols, gp.nclasses, nkt_max, splits,
              (long long)grid.x * grid.y * grid.z);
-    // Round 6: the LDS-DMA loader over pre-split planes (gather_conv_dma_kernel) for the fp16 forms on whole 16-channel blocks; AG_CONV_DMA=0: the
-    // register-staged loader (same-box A/B)
-    // the DMA loader pays for its pre-split pass (8 bytes per input element at ~5 TB/s) only where it buys the big tiles: on 128-wide tiles it is
-    // 2-4 % faster than the register-staged loader before that pass, 5-10 % slower after it (profiles/r06_conv_dma.md); AG_CONV_DMA=2 forces it everywhere
-    static const bool dma_all = [] { const char* e = getenv("AG_CONV_DMA"); return e && e[0] == '2'; }();
-    const bool dma = conv_dma_possible(gp.Cg) && xs_buf && !(terms == kF16S && bm == 64) && (dma_all || BN * bm >= 128 * 256);
-    if (dma) {
-        PresplitProblem ps_;
-        const int inst = gp.x_gs ? G : 1;
-        ps_.x = gp.xin; ps_.xs = xs_buf; ps_.amax = gp.amax_b; ps_.x_gs = gp.x_gs;
-        ps_.C = gp.Cg; ps_.Cpad = gp.Cpad; ps_.HW = gp.Hg * gp.Wg; ps_.planes = planes_of(terms);
-        ps_.xs_gs = (long long)ps_.planes * (gp.Cpad / 8) * ps_.HW * 16;
-        const int bx = std::max(1, std::min((ps_.HW + 255) / 256, 2048 / std::max(1, (gp.Cpad / 8) * inst / 8)));
-        hipLaunchKernelGGL(presplit_kernel, dim3(bx, gp.Cpad / 8, inst), dim3(256), 0, s, ps_);
-        rc = check_hip(hipGetLastError(), "presplit_kernel");
-        if (rc) return rc;
-        ProfScope ps(AG_K_GATHER_CONV, s, flops, tag);
-#define AG_LAUNCH_DMA(WMB, WNB, WVM, WVN, NTM) hipLaunchKernelGGL((gather_conv_dma_kernel<WMB, WNB, WVM, WVN, NTM>), grid, dim3(64 * WVM * WVN), 0, s, gp, (const char*)xs_buf, ps_.xs_gs)
-        if (bm == 256 && BN == 256) { if (terms == kF16S) AG_LAUNCH_DMA(4, 2, 2, 4, kF16S); else AG_LAUNCH_DMA(4, 2, 2, 4, kF16); }
-        else if (bm == 128 && BN == 256) AG_LAUNCH_DMA(2, 2, 2, 4, kF16);
-        else if (bm == 64) AG_LAUNCH_DMA(2, 2, 1, 4, kF16);
-        else if (terms == kF16S) AG_LAUNCH_DMA(2, 2, 2, 2, kF16S);
-        else AG_LAUNCH_DMA(2, 2, 2, 2, kF16);
-#undef AG_LAUNCH_DMA
-        rc = check_hip(hipGetLastError(), "gather_conv_dma_kernel");
-        if (rc || splits == 1) return rc;
-        const long long total = (long long)gp.M * cols;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        if (gp.act && gp.out_amax && blocks * G > 2048) blocks = std::max(1, 2048 / G);
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3(blocks, G), dim3(256), 0, s, gp, splits);
-        return check_hip(hipGetLastError(), "reduce_splits_kernel");
-    }
     ProfScope ps(AG_K_GATHER_CONV, s, flops, tag);      // covers the split-K finish too
     if (split) {
         const bool cexact = gp.Cg % BK == 0 && (size_t)gp.Cg * gp.Hg * gp.Wg * sizeof(float) < (size_t(1) << 32);
@@ -2194,19 +1895,10 @@ size_t ag_conv_workspace_bytes(const AgConvDesc* d)
 }  // extern "C"
 
 namespace ag {
-// the pre-split activation planes of the DMA loader (round 6): 4 bytes per element of the larger of the two tensors a gather launch may read
-static size_t presplit_bytes(const AgConvDesc* d, int G)
-{
-    int OH, OW;
-    out_size(d, OH, OW);
-    const size_t a = (size_t)round_up(d->Cin, BK) * d->H * d->W, b = (size_t)round_up(d->Cout, BK) * OH * OW;
-    return align_up((size_t)G * std::max(a, b) * 4, 256) + 256;
-}
 size_t conv_workspace_bytes_g(const AgConvDesc* d, int G)
 {
     if (validate(d) || G < 1 || G > kMaxGroups) return 0;
-    static const bool dma_on = [] { const char* e = getenv("AG_CONV_DMA"); return e && (e[0] == '1' || e[0] == '2'); }();
-    return (size_t)G * packed_bytes(d) + kMaxPartialBytes + kAmaxBytes + 512 + (dma_on ? presplit_bytes(d, G) : 0);
+    return (size_t)G * packed_bytes(d) + kMaxPartialBytes + kAmaxBytes + 512;
 }
 size_t conv_packed_bytes_g(const AgConvDesc* d, int G)
 {
@@ -2232,7 +1924,6 @@ static int run_gather_family(const AgConvDesc* d, bool backward_input, int G, co
     float* At = opt.packed ? reinterpret_cast<float*>(aligned_base(opt.packed)) : reinterpret_cast<float*>(aligned_base(workspace));
     float* partial = reinterpret_cast<float*>(aligned_base(workspace) + (size_t)G * packed_bytes(d));
     float* amax = reinterpret_cast<float*>(aligned_base(workspace) + (size_t)G * packed_bytes(d) + kMaxPartialBytes);
-    char* xs_buf = aligned_base(workspace) + align_up((size_t)G * packed_bytes(d) + kMaxPartialBytes + kAmaxBytes, 256);
 
     GatherProblem gp;
     gp.status = armed_status_word();
@@ -2263,9 +1954,7 @@ static int run_gather_family(const AgConvDesc* d, bool backward_input, int G, co
     const float* const pre_in = backward_input ? opt.amax_dy : opt.amax_x;
     if (opt.w_cin_total && opt.w_cin_total != d->Cin) { w_shape.len = (long long)d->Cin * k2; w_shape.stride = cin_rows * k2; w_shape.rows = d->Cout; }
     gp.status_tag = status_tag_of(1, M, Cg);
-    const bool scatter_ = (d->kind == AG_CONV && backward_input && d->stride == 2) || (d->kind != AG_CONV && !backward_input);
-    int bm, bn;
-    pick_tile(M, (long long)OHf * OWf / (scatter_ ? 4 : 1), G, conv_dma_possible(Cg), bm, bn);
+    const int bm = pick_bm(M);
     gp.Cg = Cg; gp.Hg = Hg; gp.Wg = Wg; gp.M = M; gp.Mpad = round_up(M, bm); gp.OHf = OHf; gp.OWf = OWf;
     gp.Cpad = round_up(Cg, BK);
     TapSet taps[kMaxClasses];
@@ -2291,7 +1980,7 @@ static int run_gather_family(const AgConvDesc* d, bool backward_input, int G, co
             for (int t = 0; t < k2; t++) { cl.dy[t] = ts.ky[t]; cl.dx[t] = ts.kx[t]; }
         }
         for (int t = k2; t < kMaxTaps; t++) cl.dy[t] = cl.dx[t] = 0;
-        return pack_and_launch(gp, taps, bm, w, stride_c, stride_m, wscale_of(d), k, At, partial, amax, w_shape, opt.amax_w, pre_in, s, opt.packed && opt.packed_valid, xs_buf, bn);
+        return pack_and_launch(gp, taps, bm, w, stride_c, stride_m, wscale_of(d), k, At, partial, amax, w_shape, opt.amax_w, pre_in, s, opt.packed && opt.packed_valid);
     }
     // scatter with stride 2: output coordinate o = 2*i + ky - poff  (poff = padding for the conv gradient, 0 for convT).
     // Class (qy, qx) = parity of the output coordinate; it receives only taps with ky = (o + poff) mod 2, from
@@ -2329,7 +2018,7 @@ static int run_gather_family(const AgConvDesc* d, bool backward_input, int G, co
             gp.cls[pos] = cl; taps[pos] = ts;
             gp.nclasses++;
         }
-    return pack_and_launch(gp, taps, bm, w, stride_c, stride_m, wscale_of(d), k, At, partial, amax, w_shape, opt.amax_w, pre_in, s, opt.packed && opt.packed_valid, xs_buf, bn);
+    return pack_and_launch(gp, taps, bm, w, stride_c, stride_m, wscale_of(d), k, At, partial, amax, w_shape, opt.amax_w, pre_in, s, opt.packed && opt.packed_valid);
 }
 
 }  // extern "C"
@@ -2395,10 +2084,9 @@ int conv_backward_weight_g(const AgConvDesc* d, int G, const float* x, long long
     {
         // Round 5 (second session): since the slices are stored and added by wgrad_reduce_kernel (no atomics), a split costs one more write and one
         // more read of the whole [G][Mpad][Npad] tile set, at ~3 TB/s, in units of a K tile's time (0.45 us) -- 84 units per slice for the
-        // 512 x 512 x 9, G = 6 layers, whose K loop is 256 tiles: the model now knows (AG_WGRAD_SPLIT_MODEL=0: the round-2 model, for the A/B)
-        static const bool traffic_aware = [] { const char* e = getenv("AG_WGRAD_SPLIT_MODEL"); return !(e && e[0] == '0'); }();
+        // 512 x 512 x 9, G = 6 layers, whose K loop is 256 tiles: the per_split term below accounts for that
         const double set_bytes = (double)G * round_up(wp.Mw, bm) * round_up(Nw, BN) * sizeof(float);
-        const double per_split = traffic_aware ? 2.0 * set_bytes / 3e12 / 0.45e-6 : 0.0;
+        const double per_split = 2.0 * set_bytes / 3e12 / 0.45e-6;
         double best_cost = 1e30;
         const int smax = std::max(1, std::min(nkt_all / 8, 4096));
         for (int sp = 1; sp <= smax; sp++) {
@@ -2462,9 +2150,8 @@ int conv_backward_weight_g(const AgConvDesc* d, int G, const float* x, long long
 #define AG_LAUNCH_WSPLIT_V(WMB, WNB) do { if (terms == 6) AG_LAUNCH_WSPLIT_VT(WMB, WNB, 6); else if (terms == 3) AG_LAUNCH_WSPLIT_VT(WMB, WNB, 3); \
                                           else if (terms == kF16S) AG_LAUNCH_WSPLIT_VT(WMB, WNB, kF16S); else AG_LAUNCH_WSPLIT_VT(WMB, WNB, kF16); } while (0)
         // the K-vectorised loader of the gathered operand: stride-1 "same" convolutions with rows of a multiple of 16 pixels (every 3 x 3 stride-1
-        // layer of the product), whole K tiles per slice; AG_WGRAD_BVEC=0 keeps the scalar gathers (A/B)
-        static const bool bvec_on = [] { const char* e = getenv("AG_WGRAD_BVEC"); return !(e && e[0] == '0'); }();
-        const bool bvec = bvec_on && avec && d->kind == AG_CONV && d->stride == 1 && wp.gw == wp.Wg && wp.gh == wp.Hg && (wp.gw & 15) == 0 && wp.gw >= 16 &&
+        // layer of the product), whole K tiles per slice; every other shape takes the scalar gathers
+        const bool bvec = avec && d->kind == AG_CONV && d->stride == 1 && wp.gw == wp.Wg && wp.gh == wp.Hg && (wp.gw & 15) == 0 && wp.gw >= 16 &&
                           (Kp & 15) == 0 && (wp.ksplit_len & 15) == 0 && 2 * d->padding + 1 == k && k <= 3;
         if (bvec) {
             if (bm == 64) AG_LAUNCH_WSPLIT_V(1, 2); else AG_LAUNCH_WSPLIT_V(2, 1);
@@ -2489,11 +2176,10 @@ int conv_backward_weight_g(const AgConvDesc* d, int G, const float* x, long long
     wr.partial = wp.partial; wr.G = G; wr.splits = splits; wr.Mw = wp.Mw; wr.Nw = Nw; wr.Mpad = wp.Mpad; wr.Npad = wp.Npad; wr.ntaps = k2;
     wr.c_row_stride = wp.c_row_stride; wr.c_chan_stride = wp.c_chan_stride;
     const long long total = (long long)wp.Mw * Nw;
-    // many terms per element (the few-tile layers at large images): the terms of an element over 8 or 16 threads; AG_WGRAD_REDUCE_PAR=0: always
-    // the one-thread-per-element kernel (the A/B)
-    static const bool par_on = [] { const char* e = getenv("AG_WGRAD_REDUCE_PAR"); return !(e && e[0] == '0'); }();
+    // many terms per element (the few-tile layers at large images): the terms of an element over 8 or 16 threads; fewer than 8: the
+    // one-thread-per-element kernel
     const int terms_per_elem = splits * longest_run;
-    if (par_on && terms_per_elem >= 8) {
+    if (terms_per_elem >= 8) {
         if (terms_per_elem >= 48)
             hipLaunchKernelGGL(wgrad_reduce_par_kernel<16>, dim3((unsigned)std::min<long long>((total + 15) / 16, 8192), nruns), dim3(256), 0, s, wr);
         else
@@ -2536,19 +2222,5 @@ int ag_conv_set_math(int mode)
 int ag_conv_get_math(void) { return g_conv_math.load(std::memory_order_relaxed); }
 
 int ag_conv_status(int clear) { return take_status(clear != 0); }
-
-
-
-int ag_debug_mfma_rate_bf16(int blocks, int iters, float* out, void* stream)
-{
-    hipLaunchKernelGGL(mfma_rate_bf16_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), iters, out);
-    return check_hip(hipGetLastError(), "mfma_rate_bf16_kernel");
-}
-
-int ag_debug_mfma_rate(int blocks, int iters, float* out, void* stream)
-{
-    hipLaunchKernelGGL(mfma_rate_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), iters, out);
-    return check_hip(hipGetLastError(), "mfma_rate_kernel");
-}
 
 }  // extern "C"

@@ -61,8 +61,6 @@ int ag_conv_backward_input(const AgConvDesc* d, const float* dy, const float* w,
 int ag_conv_backward_weight(const AgConvDesc* d, const float* x, const float* dy, float* dw, void* workspace,
                             size_t workspace_bytes, void* stream);
 
-/* Calibration: `blocks` x 4 waves each issue iters x 4 independent v_mfma_f32_32x32x2_f32 (8192 FLOP each per wave) with
- * no memory traffic; time it to get the attainable fp32 MFMA rate of the device (profiles/mfma_peak.py). */
 /* Arithmetic of the MFMA convolutions (process-wide; the pointwise VALU kernels are plain fp32 either way).
  *   AG_CONV_MATH_FP32_MFMA     v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation.
  *   AG_CONV_MATH_SPLIT_F16     (default since round 4) every operand tensor scaled by a power of two that puts its largest magnitude M into
@@ -102,10 +100,6 @@ int ag_conv_get_math(void);
  * (in the fp32 / bf16 forms a non-finite operand propagates into the outputs as it does through the reference's cuDNN calls, and nothing is
  * refused), and the flag carries which launch raised it (kernel kind, output rows, gathered channels: named in ag_last_error). */
 int ag_conv_status(int clear);
-
-int ag_debug_mfma_rate(int blocks, int iters, float* out, void* stream);
-/* Same for v_mfma_f32_32x32x16_bf16 (calibration of the bf16-split option; not used by the product). */
-int ag_debug_mfma_rate_bf16(int blocks, int iters, float* out, void* stream);
 
 #ifdef __cplusplus
 }
