@@ -1,11 +1,13 @@
 """MI355X-native Animatable Gaussians.  The modules are imported by name (``from animatablegaussians_amd import losses``); the two
-loader-facing functions of ``targets``, the template stage's ``TemplateField`` and its renderer (``render``, ``near_far_smpl``,
-``sample_pts_on_rays``, ``composite`` of ``template_render``) are also reachable from the package, resolved on first use so that importing
-the package stays free of side effects."""
+loader-facing functions of ``targets``, the template stage's ``TemplateField`` with ``eikonal_loss`` and its renderer (``render``,
+``render_normals``, ``near_far_smpl``, ``sample_pts_on_rays``, ``composite`` of ``template_render``) are also reachable from the package,
+resolved on first use so that importing the package stays free of side effects."""
 
-__all__ = ["prepare_targets", "boundary_mask", "TemplateField", "render", "near_far_smpl", "sample_pts_on_rays", "composite"]
+__all__ = ["prepare_targets", "boundary_mask", "TemplateField", "eikonal_loss", "render", "render_normals", "near_far_smpl",
+           "sample_pts_on_rays", "composite"]
 
-_HOME = {"prepare_targets": "targets", "boundary_mask": "targets", "TemplateField": "template_field", "render": "template_render",
+_HOME = {"prepare_targets": "targets", "boundary_mask": "targets", "TemplateField": "template_field", "eikonal_loss": "template_field",
+         "render": "template_render", "render_normals": "template_render",
          "near_far_smpl": "template_render", "sample_pts_on_rays": "template_render", "composite": "template_render"}
 
 

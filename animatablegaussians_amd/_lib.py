@@ -296,6 +296,8 @@ SYMBOLS = [
     ("ag_template_field_desc_bytes", c_sz, []),
     ("ag_template_field_blob_floats", c_sz, [ctypes.POINTER(AgTemplateFieldDesc)]),
     ("ag_template_field_forward", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
+    # include/ag_template_field_grad.h
+    ("ag_template_field_sdf_grad", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_ray_march.h
     ("ag_ray_near_far", ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, ctypes.c_int64, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("ag_ray_sample", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

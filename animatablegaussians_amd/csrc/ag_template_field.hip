@@ -1,4 +1,5 @@
-// The template stage's field (include/ag_template_field.h): embedding -> geometry MLP -> colour MLP -> density, one fused forward kernel.
+// The template stage's field (include/ag_template_field.h): embedding -> geometry MLP -> colour MLP -> density, one fused forward kernel;
+// below it the SDF with its gradient (include/ag_template_field_grad.h), a second kernel of the same shape.
 //
 // Shape.  A workgroup of 8 waves owns a tile of kPoints = 32 points and keeps it in LDS from the embedding to the outputs:
 //   emb   [32][kEmbStride]   the positional embedding (columns 0 .. 63) and the view embedding (64 .. 95), padding columns zero;
@@ -16,6 +17,7 @@
 // Compiled WITHOUT fp contraction (build.sh EXACT): the header states the embedding, the activations and the density op by op.
 #include "ag_common.h"
 #include "../../include/ag_template_field.h"
+#include "../../include/ag_template_field_grad.h"
 
 #include <cmath>
 
@@ -176,6 +178,137 @@ __global__ void __launch_bounds__(kThreads) template_field_kernel(Plan plan, con
     }
 }
 
+// ---- the SDF with its gradient (include/ag_template_field_grad.h) ------------------------------------------------------------------------
+// Forward mode: a tile is kGradPoints = 8 points x 4 rows, MFMA row 4 q + c with q the point, c = 0 its value row and c = 1 .. 3 the
+// tangent d/dx_{c-1}.  A tangent row goes through the same linear maps as the value row (from 0 instead of the bias) and is multiplied
+// by the activation's derivative at the value row's pre-activation.  In the C/D map a lane holds rows (r & 3) + 8 (r >> 2) + 4 h: c = r & 3
+// and q = 2 (r >> 2) + h, so acc[4 j .. 4 j + 3] are the value and the three tangents of ONE point and the derivative needs no other lane.
+// The value rows see the instructions of template_field_kernel (a row of an MFMA does not depend on the other rows), so sdf and
+// density are that kernel's bit for bit.  Same LDS, same blob, same plan as an SDF-only forward.
+constexpr int kGradPoints = kPoints / 4;
+
+__device__ __forceinline__ float activation_slope(float z, int act, float beta)
+{
+    if (act == AG_FIELD_ACT_SOFTPLUS) {
+        const float bz = beta * z;
+        return bz > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-bz));
+    }
+    if (act == AG_FIELD_ACT_RELU) return z > 0.0f ? 1.0f : 0.0f;
+    return 1.0f;
+}
+
+// emb(x, L) of 8 points into rows 4 q and its three tangents into rows 4 q + 1 + b, columns [0, pad8(3 + 6 L)); a point past N reads as zero
+__device__ __forceinline__ void embed_tile_grad(float* emb, int L, const float* __restrict__ src, long long p0, long long N)
+{
+    const int per_point = 3 * (L + 1);
+    for (int e = threadIdx.x; e < kGradPoints * per_point; e += kThreads) {
+        const int q = e / per_point, r = e - q * per_point;
+        const int fi = r / 3, axis = r - 3 * fi;
+        const float x = p0 + q < N ? src[(size_t)(p0 + q) * 3 + axis] : 0.0f;
+        float* row = emb + 4 * q * kEmbStride;
+        if (fi == 0) {
+            row[axis] = x;
+            for (int b = 0; b < 3; ++b) row[(1 + b) * kEmbStride + axis] = b == axis ? 1.0f : 0.0f;
+        } else {
+            const float f = (float)(1 << (fi - 1));
+            const float v = x * f;
+            const float s = sinf(v), c = cosf(v);
+            const int cs = 3 + 6 * (fi - 1) + axis, cc = cs + 3;
+            row[cs] = s;
+            row[cc] = c;
+            for (int b = 0; b < 3; ++b) {
+                row[(1 + b) * kEmbStride + cs] = b == axis ? f * c : 0.0f;
+                row[(1 + b) * kEmbStride + cc] = b == axis ? -(f * s) : 0.0f;
+            }
+        }
+    }
+    const int cols = 3 + 6 * L, pad = (cols + 7) / 8 * 8 - cols;
+    for (int e = threadIdx.x; e < kPoints * pad; e += kThreads) emb[(e / pad) * kEmbStride + cols + e % pad] = 0.0f;
+}
+
+__global__ void __launch_bounds__(kThreads) template_field_grad_kernel(Plan plan, const float* __restrict__ blob, const float* __restrict__ xyz, long long N,
+                                                                       long long n_tiles, float* __restrict__ sdf, float* __restrict__ grad,
+                                                                       float* __restrict__ density)
+{
+    __shared__ __attribute__((aligned(16))) float act_lds[2 * kPoints * kActStride];
+    __shared__ __attribute__((aligned(16))) float emb[kPoints * kEmbStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 31, h = lane >> 5;
+    const float alpha = 1.0f / plan.b;
+
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long long p0 = tile * kGradPoints;
+        embed_tile_grad(emb, plan.L, xyz, p0, N);
+        __syncthreads();
+        float* in = act_lds + kPoints * kActStride;
+        float* out = act_lds;
+        for (int l = 0; l < plan.n_layers; ++l) {
+            const LayerPlan lp = plan.layer[l];
+            const int n_col_tiles = lp.Np >> 5;
+            const size_t wstep = 2 * (size_t)lp.Np;                    // float4s between two groups of 8 k
+            for (int t = lp.first_tile + wave; t < n_col_tiles; t += kWaves) {
+                const int n = t * 32 + i;
+                const float bias = blob[lp.b_off + n];
+                f32x16 acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = (r & 3) == 0 ? bias : 0.0f;
+                // the operand reads and the MFMA order of template_field_kernel
+                const float4* w = reinterpret_cast<const float4*>(blob + lp.w_off) + (size_t)h * lp.Np + n;
+                const float* a = in + i * kActStride + 4 * h;
+                const int ga = lp.Ka >> 3, ge = lp.Ke >> 3;
+                float4 av[4], wv[4];
+                if (ga > 0) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { av[j] = *reinterpret_cast<const float4*>(a + 8 * j); wv[j] = w[j * wstep]; }
+                }
+                for (int g = 0; g < ga; g += 4) {
+                    float4 an[4], wn[4];
+                    const int gn = g + 4 < ga ? g + 4 : g;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { an[j] = *reinterpret_cast<const float4*>(a + 8 * (gn + j)); wn[j] = w[(gn + j) * wstep]; }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc = mac8(acc, av[j], wv[j]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { av[j] = an[j]; wv[j] = wn[j]; }
+                }
+                w += ga * wstep;
+                const float* e = emb + i * kEmbStride + lp.emb_off + 4 * h;
+                for (int g = 0; g < ge; ++g) acc = mac8(acc, *reinterpret_cast<const float4*>(e + 8 * g), w[g * wstep]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float z = acc[4 * j];
+                    const float v = activate(z, lp.act, plan.beta);
+                    const float slope = activation_slope(z, lp.act, plan.beta);
+                    const float t0 = acc[4 * j + 1] * slope, t1 = acc[4 * j + 2] * slope, t2 = acc[4 * j + 3] * slope;
+                    if (lp.route == kGeoLast) {                        // first_tile: only the SDF tile runs
+                        const long long p = p0 + 2 * j + h;
+                        if (i == 0 && p < N) {
+                            sdf[p] = -v;
+                            grad[(size_t)p * 3 + 0] = t0;
+                            grad[(size_t)p * 3 + 1] = t1;
+                            grad[(size_t)p * 3 + 2] = t2;
+                            if (density != nullptr) {
+                                const float sgn = v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f);
+                                const float em = expm1f(-fabsf(v) / plan.b);
+                                density[p] = alpha * (0.5f + (0.5f * sgn) * em);
+                            }
+                        }
+                    } else {
+                        float* o = out + (8 * j + 4 * h) * kActStride + n;
+                        o[0] = v;
+                        o[kActStride] = t0;
+                        o[2 * kActStride] = t1;
+                        o[3 * kActStride] = t2;
+                    }
+                }
+            }
+            __syncthreads();
+            float* s = in; in = out; out = s;
+        }
+    }
+}
+
 inline int pad8(int v) { return (v + 7) / 8 * 8; }
 inline int pad32(int v) { return (v + 31) / 32 * 32; }
 
@@ -291,4 +424,31 @@ extern "C" int ag_template_field_forward(const AgTemplateFieldDesc* desc, const 
     hipLaunchKernelGGL(template_field_kernel, dim3((unsigned)grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), plan, blob, xyz, viewdirs,
                        (long long)N, n_tiles, sdf, density, color);
     return check_hip(hipGetLastError(), "template_field_kernel");
+}
+
+extern "C" int ag_template_field_sdf_grad(const AgTemplateFieldDesc* desc, const float* blob, size_t blob_floats, const float* xyz, int64_t N, float* sdf,
+                                          float* grad, float* density, void* stream)
+{
+    Plan plan;
+    size_t total = 0;
+    if (int rc = make_plan(desc, false, plan, total)) return rc;
+    for (int l = 0; l < desc->n_geo; ++l) {
+        if (desc->geo[l].concat == AG_FIELD_CONCAT_VIEW) {
+            set_error("template field gradient: geometry layer %d concatenates the view embedding, and there are no view directions here", l);
+            return AG_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (N < 0) { set_error("template field: N = %lld is negative", (long long)N); return AG_ERR_INVALID_ARGUMENT; }
+    if (blob_floats != total) { set_error("template field: blob of %zu floats, %zu expected for this table", blob_floats, total); return AG_ERR_INVALID_ARGUMENT; }
+    if (N == 0) return AG_OK;
+    if (!blob || !xyz || !sdf || !grad) { set_error("null pointer in ag_template_field_sdf_grad"); return AG_ERR_INVALID_ARGUMENT; }
+    if (reinterpret_cast<uintptr_t>(blob) % 16 != 0) { set_error("template field: the blob is not 16-byte aligned"); return AG_ERR_INVALID_ARGUMENT; }
+    int dev = 0, cus = 0;
+    if (int rc = check_hip(hipGetDevice(&dev), "template field hipGetDevice")) return rc;
+    if (int rc = check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "template field CU count")) return rc;
+    const long long n_tiles = (N + kGradPoints - 1) / kGradPoints;
+    const long long grid = n_tiles < 4ll * cus ? n_tiles : 4ll * cus;          // as ag_template_field_forward
+    hipLaunchKernelGGL(template_field_grad_kernel, dim3((unsigned)grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), plan, blob, xyz, (long long)N,
+                       n_tiles, sdf, grad, density);
+    return check_hip(hipGetLastError(), "template_field_grad_kernel");
 }

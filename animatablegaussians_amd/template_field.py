@@ -6,7 +6,11 @@ positional embedding (``utils/embedder.py``), the weight-normalised ``SdfMLP`` a
 the outputs.  ``sdf_grid`` / ``extract_mesh`` are ``TemplateTrainer.test_geometry`` in canonical space (``main_template.py:103-133``): a
 reference template checkpoint becomes the mesh that ``obj_io.save_mesh_ply`` writes as ``template.ply``.
 
-NOT here: the hand fusion (``fuse_hands``), the gradient of the SDF (``compute_grad``, training only), any backward.  Ray sampling and
+``sdf_normal`` is the same function with ``compute_grad`` (``template.py:129-139``): the gradient of the raw SDF with respect to the points,
+the reference's ``'normal'``, by a second fused kernel that pushes three tangents through the geometry MLP beside the value
+(``include/ag_template_field_grad.h``); ``eikonal_loss`` is ``main_template.py:53-58`` on it.
+
+NOT here: the hand fusion (``fuse_hands``), any gradient with respect to the weights (template training), any backward.  Ray sampling and
 compositing, the other half of ``TemplateNet.render``, are ``template_render.py``.  Every tensor must be on the GPU; there is no host path
 and no PyTorch fallback.
 """
@@ -112,6 +116,19 @@ def volume_points(axes, x0: int, x1: int) -> torch.Tensor:
     pts[..., 1] = ay.view(1, ny, 1)
     pts[..., 2] = az.view(1, 1, nz)
     return pts.view(-1, 3)
+
+
+def _points(xyz) -> torch.Tensor:
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise ValueError("xyz must be a tensor on the GPU (there is no host path)")
+    if xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"xyz must be float32 [N, 3], got {xyz.dtype} {tuple(xyz.shape)}")
+    return xyz.detach().contiguous()
+
+
+def eikonal_loss(normal: torch.Tensor) -> torch.Tensor:
+    """``((||normal||_2 - 1)^2).mean()`` over the last axis (``main_template.py:55``), in torch ops on the tensor's device."""
+    return ((torch.linalg.norm(normal, ord=2, dim=-1) - 1.0) ** 2).mean()
 
 
 class TemplateField:
@@ -284,11 +301,7 @@ class TemplateField:
             raise ValueError(f"want names 'sdf', 'density', 'color', got {want}")
         if "color" in want and not self.color:
             raise ValueError("this field has no colour MLP")
-        if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
-            raise ValueError("xyz must be a tensor on the GPU (there is no host path)")
-        if xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
-            raise ValueError(f"xyz must be float32 [N, 3], got {xyz.dtype} {tuple(xyz.shape)}")
-        xyz = xyz.detach().contiguous()
+        xyz = _points(xyz)
         if viewdirs is not None:
             if not isinstance(viewdirs, torch.Tensor) or viewdirs.device != xyz.device:
                 raise ValueError("viewdirs must be a tensor on the device of xyz")
@@ -305,6 +318,36 @@ class TemplateField:
             self._forward(xyz, viewdirs, out["sdf"], out.get("density"), out.get("color"))
         out["cano_xyz"] = xyz
         return out
+
+    def sdf_normal(self, xyz: torch.Tensor, want=("sdf", "normal")):
+        """``forward_cano_body_nerf`` with ``compute_grad``: ``xyz`` [N, 3] float32 on the GPU -> dict of device tensors: ``sdf`` [N, 1],
+        ``normal`` [N, 3] (both always), ``density`` [N, 1] when named in ``want``, and ``cano_xyz``.  ``normal`` is the reference's: the
+        gradient of the RAW SDF (minus the gradient of ``sdf``) with respect to the points, NOT normalised; it points out of the body.
+        ``sdf`` and ``density`` are ``__call__``'s bit for bit.  The colour MLP does not run and view directions play no part."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not set(want) <= {"sdf", "normal", "density"}:
+            raise ValueError(f"want names 'sdf', 'normal', 'density', got {want}")
+        xyz = _points(xyz)
+        n, dev = xyz.shape[0], xyz.device
+        out = {"sdf": torch.empty((n, 1), dtype=torch.float32, device=dev), "normal": torch.empty((n, 3), dtype=torch.float32, device=dev)}
+        if "density" in want:
+            out["density"] = torch.empty((n, 1), dtype=torch.float32, device=dev)
+        if n:
+            blob = self._blob_on(dev)
+            d = self.desc()
+            p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+            with _lib.on_device(dev):
+                stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                _lib.check(_lib.lib().ag_template_field_sdf_grad(ctypes.byref(d), p(blob), blob.numel(), p(xyz), n, p(out["sdf"]), p(out["normal"]),
+                                                                 p(out.get("density")), stream), "ag_template_field_sdf_grad")
+        out["cano_xyz"] = xyz
+        return out
+
+    def surface_normals(self, points: torch.Tensor) -> torch.Tensor:
+        """Unit normals [N, 3] of the level set through each of ``points``: ``normal / max(||normal||, 1e-12)``.  They point outward, the
+        orientation of the normals ``extract_mesh`` returns."""
+        n = self.sdf_normal(points)["normal"]
+        return n / torch.linalg.norm(n, dim=-1, keepdim=True).clamp_min(1e-12)
 
     def sdf_grid(self, bounds, res, device=None) -> torch.Tensor:
         """The SDF at the nodes of ``net_util.generate_volume_points(bounds, res)`` as ``[X, Y, Z]`` float32 on ``device`` (default: the

@@ -6,7 +6,10 @@ kernels and the two that existed: near / far of every ray against balls around t
 posed space (``inverse_skinning``), the fused field (``template_field.TemplateField``) and alpha compositing (``template.py:372-374``,
 ``nerf_util.raw2outputs``).  The random numbers of a perturbed sampling are the caller's (``u``), never a kernel's.
 
-NOT here: the hand fusion (``fuse_hands``), ``compute_grad`` / normals, any backward, the training-mode noise on the view directions, the
+``render_normals`` is the same march with ``compute_grad``: the raw SDF gradient at every sample (``render_output['normal']``,
+``template.py:380-383``) from ``TemplateField.sdf_normal``, and a composited normal image.
+
+NOT here: the hand fusion (``fuse_hands``), any backward, the training-mode noise on the view directions, the
 scattering through ``mask_within_patch`` and the dataset-side ray selection of ``nerf_util`` (``get_rays``, ``get_near_far``, patch
 sampling): the caller brings the rays and the box near / far, as the reference's batch does.  Near / far is pinned to the header's
 formulas: the reference's kernel is CUDA and was never run beside this one.  Every tensor must be on the GPU; there is no host path
@@ -176,30 +179,9 @@ def composite(density: torch.Tensor, color: Optional[torch.Tensor], z_vals: torc
     return {k: v for k, v in out.items() if k in want}
 
 
-def render(field, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.Tensor, far: torch.Tensor, *, space: str = "cano", sampling: str = "smpl",
-           live_smpl_v: Optional[torch.Tensor] = None, radius: float = 0.1, dist: Optional[torch.Tensor] = None,
-           near_sur_dist: Optional[float] = None, n_samples: int = 64, u: Optional[torch.Tensor] = None, chunk_size: int = 4096,
-           white_bkgd: bool = False, live: Optional[dict] = None, want=("rgb_map", "acc_map")):
-    """``TemplateNet.render`` in eval mode for one batch element: rays ``ray_o`` / ``ray_d`` [R, 3] (or [1, R, 3]) with the box ``near`` /
-    ``far`` [R] (or [1, R]) through ``field`` (a ``TemplateField``) -> dict of ``rgb_map`` [R, 3], ``acc_map`` [R] and, when named in
-    ``want``, ``depth_map``, ``disp_map``, ``weights`` [R, S]; a leading 1 of the rays is kept in the outputs.
-
-    ``sampling`` (the reference's ``depth_guided_sampling``): ``"smpl"`` takes near / far from ``near_far_smpl(live_smpl_v, ..)`` with
-    the given ones for the rays that hit nothing, 64 samples; ``"uniform"`` the given ones, 64 samples; ``"depth"`` ``dist -+
-    near_sur_dist`` where ``dist`` [R] ``> 1e-6`` and the given ones elsewhere, ``n_samples`` samples.  ``u`` [R, S] perturbs the samples
-    (the reference's training mode; with ``"depth"`` only the rays with a valid ``dist``, ``template.py:334``).
-
-    ``space="live"`` maps every sample to canonical space first: ``live`` holds the arguments of
-    ``inverse_skinning.transform_live2cano`` by name (``cano2live_jnt_mats``, ``volume``, ``live_mesh_v``, ``live_mesh_f``,
-    ``live_mesh_lbs`` and optionally ``near_thres``, ``use_root_finding``, ``with_hand`` ..).  The rays are processed ``chunk_size`` at
-    a time: sample, map, field, composite straight into the outputs; nothing depends on ``chunk_size``, bit for bit.  A field without
-    a colour MLP renders everything but ``rgb_map``."""
-    from .template_field import TemplateField
-    if not isinstance(field, TemplateField):
-        raise ValueError("field must be a TemplateField")
-    want = _want(want)
-    if "rgb_map" in want and not field.color:
-        raise ValueError("this field has no colour MLP: rgb_map cannot be rendered")
+def _march_setup(ray_o, ray_d, near, far, space, sampling, live_smpl_v, radius, dist, near_sur_dist, n_samples, u, chunk_size, live):
+    """The checks and the sampling set-up that ``render`` and ``render_normals`` share, after their own checks of ``want``: ->
+    ``(o, d, near, far, t, u, mask, chunk_size, batched)`` with near / far already those of the sampling.  A refusal launches nothing."""
     if space not in ("cano", "live"):
         raise ValueError(f"space must be 'cano' or 'live', got {space!r}")
     if sampling not in SAMPLINGS:
@@ -242,20 +224,96 @@ def render(field, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.Tensor, 
     u, mask = _perturbation(u, mask if u is not None else None, R, S, dev)
     if sampling == "smpl":                          # after every check: a refusal launches nothing
         near, far, _ = near_far_smpl(v, o, d, radius, fallback=(near, far))
-    t = _t_vals(S, dev)
-    out = _outputs(want, R, S, dev)
-    field_want = ("sdf", "density", "color") if "rgb_map" in want else ("sdf", "density")
-    use_dirs = bool(field.use_viewdir) and "rgb_map" in want
+    return o, d, near, far, _t_vals(S, dev), u, mask, chunk_size, batched
+
+
+def _chunks(setup, space, live, want_dirs):
+    """``(r0, r1, canonical points [(r1 - r0) * S, 3], z [r1 - r0, S], dirs or None)`` of every chunk of rays: sample, then (live) map."""
+    o, d, near, far, t, u, mask, chunk_size, _ = setup
     if space == "live":
         from .inverse_skinning import transform_live2cano
-    for r0 in range(0, R, chunk_size):
-        r1 = min(R, r0 + chunk_size)
+    for r0 in range(0, o.shape[0], chunk_size):
+        r1 = min(o.shape[0], r0 + chunk_size)
         pts, z, dirs = _sample(o[r0:r1], d[r0:r1], near[r0:r1], far[r0:r1], t, None if u is None else u[r0:r1], None if mask is None else mask[r0:r1],
-                               use_dirs)
+                               want_dirs)
         pts = pts.view(-1, 3)
         if space == "live":
             pts = transform_live2cano(pts[None], **live)[0][0]
+        yield r0, r1, pts, z, dirs
+
+
+def render(field, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.Tensor, far: torch.Tensor, *, space: str = "cano", sampling: str = "smpl",
+           live_smpl_v: Optional[torch.Tensor] = None, radius: float = 0.1, dist: Optional[torch.Tensor] = None,
+           near_sur_dist: Optional[float] = None, n_samples: int = 64, u: Optional[torch.Tensor] = None, chunk_size: int = 4096,
+           white_bkgd: bool = False, live: Optional[dict] = None, want=("rgb_map", "acc_map")):
+    """``TemplateNet.render`` in eval mode for one batch element: rays ``ray_o`` / ``ray_d`` [R, 3] (or [1, R, 3]) with the box ``near`` /
+    ``far`` [R] (or [1, R]) through ``field`` (a ``TemplateField``) -> dict of ``rgb_map`` [R, 3], ``acc_map`` [R] and, when named in
+    ``want``, ``depth_map``, ``disp_map``, ``weights`` [R, S]; a leading 1 of the rays is kept in the outputs.
+
+    ``sampling`` (the reference's ``depth_guided_sampling``): ``"smpl"`` takes near / far from ``near_far_smpl(live_smpl_v, ..)`` with
+    the given ones for the rays that hit nothing, 64 samples; ``"uniform"`` the given ones, 64 samples; ``"depth"`` ``dist -+
+    near_sur_dist`` where ``dist`` [R] ``> 1e-6`` and the given ones elsewhere, ``n_samples`` samples.  ``u`` [R, S] perturbs the samples
+    (the reference's training mode; with ``"depth"`` only the rays with a valid ``dist``, ``template.py:334``).
+
+    ``space="live"`` maps every sample to canonical space first: ``live`` holds the arguments of
+    ``inverse_skinning.transform_live2cano`` by name (``cano2live_jnt_mats``, ``volume``, ``live_mesh_v``, ``live_mesh_f``,
+    ``live_mesh_lbs`` and optionally ``near_thres``, ``use_root_finding``, ``with_hand`` ..).  The rays are processed ``chunk_size`` at
+    a time: sample, map, field, composite straight into the outputs; nothing depends on ``chunk_size``, bit for bit.  A field without
+    a colour MLP renders everything but ``rgb_map``."""
+    from .template_field import TemplateField
+    if not isinstance(field, TemplateField):
+        raise ValueError("field must be a TemplateField")
+    want = _want(want)
+    if "rgb_map" in want and not field.color:
+        raise ValueError("this field has no colour MLP: rgb_map cannot be rendered")
+    setup = _march_setup(ray_o, ray_d, near, far, space, sampling, live_smpl_v, radius, dist, near_sur_dist, n_samples, u, chunk_size, live)
+    o, t, batched = setup[0], setup[4], setup[8]
+    out = _outputs(want, o.shape[0], t.shape[0], o.device)
+    field_want = ("sdf", "density", "color") if "rgb_map" in want else ("sdf", "density")
+    use_dirs = bool(field.use_viewdir) and "rgb_map" in want
+    for r0, r1, pts, z, dirs in _chunks(setup, space, live, use_dirs):
         ret = field(pts, dirs.view(-1, 3) if use_dirs else None, want=field_want)
         _composite_into(ret["density"], ret.get("color"), z, white_bkgd, {k: v[r0:r1] for k, v in out.items()})
+    out = {k: v for k, v in out.items() if k in want}
+    return {k: v[None] for k, v in out.items()} if batched else out
+
+
+NORMAL_OUTPUTS = ("normal", "normal_map", "acc_map", "depth_map", "weights")
+
+
+def render_normals(field, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.Tensor, far: torch.Tensor, *, space: str = "cano", sampling: str = "smpl",
+                   live_smpl_v: Optional[torch.Tensor] = None, radius: float = 0.1, dist: Optional[torch.Tensor] = None,
+                   near_sur_dist: Optional[float] = None, n_samples: int = 64, u: Optional[torch.Tensor] = None, chunk_size: int = 4096,
+                   live: Optional[dict] = None, want=("normal_map", "acc_map")):
+    """``render``'s rays, samplings, spaces and checks with ``compute_grad`` (``template.py:380-383``) -> dict of
+
+    ``normal`` [R, S, 3] (only when named in ``want``): the reference's ``render_output['normal']``, the raw gradient of the SDF at
+    every sample (``TemplateField.sdf_normal``), in CANONICAL coordinates also for ``space="live"``: the reference differentiates with
+    respect to the canonical points;
+    ``normal_map`` [R, 3] ``= sum_s weights_s * n_s / max(||n_s||, 1e-12)``: the unit normals composited as ``render`` composites the
+    colour, without a background.  This is this project's definition; the reference has no normal image;
+    ``acc_map`` [R] (``render``'s bit for bit) and, when named, ``depth_map`` [R], ``weights`` [R, S].
+
+    Per chunk: sample, map, one ``ag_template_field_sdf_grad`` launch, composite; nothing depends on ``chunk_size``, bit for bit."""
+    from .template_field import TemplateField
+    if not isinstance(field, TemplateField):
+        raise ValueError("field must be a TemplateField")
+    want = _want(want, NORMAL_OUTPUTS)
+    setup = _march_setup(ray_o, ray_d, near, far, space, sampling, live_smpl_v, radius, dist, near_sur_dist, n_samples, u, chunk_size, live)
+    o, t, batched = setup[0], setup[4], setup[8]
+    R, S, dev = o.shape[0], t.shape[0], o.device
+    out = _outputs(tuple(k for k in want if k in OUTPUTS) + (("rgb_map",) if "normal_map" in want else ()), R, S, dev)
+    normal = torch.empty((R, S, 3), dtype=torch.float32, device=dev) if "normal" in want else None
+    for r0, r1, pts, z, _ in _chunks(setup, space, live, False):
+        ret = field.sdf_normal(pts, want=("sdf", "normal", "density"))
+        n = ret["normal"]
+        if normal is not None:
+            normal[r0:r1] = n.view(r1 - r0, S, 3)
+        unit = n / torch.linalg.norm(n, dim=-1, keepdim=True).clamp_min(1e-12) if "normal_map" in want else None
+        _composite_into(ret["density"], unit, z, False, {k: v[r0:r1] for k, v in out.items()})
+    if "normal_map" in want:
+        out["normal_map"] = out.pop("rgb_map")
+    if normal is not None:
+        out["normal"] = normal
     out = {k: v for k, v in out.items() if k in want}
     return {k: v[None] for k, v in out.items()} if batched else out

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Time the template field's SDF grid at the workload's own shape, against the same layers as a plain torch chain.
 
-    python profiles/template_field.py [--res 256 256 128] [--iters 2] [--runs 2]
+    python profiles/template_field.py [--res 256 256 128] [--iters 2] [--runs 2] [--grad]
 
 The reference architecture (multires 6; 39 -> 512 -> 256 -> 256 -> 256 -> (256 + 39) -> 256 -> 257, Softplus(beta = 100); weights of a
 deterministic recipe with the shapes of the geometric initialisation, every weight perturbed) is evaluated at the nodes of the
@@ -12,6 +12,12 @@ reference's ``testing_res`` grid (256, 256, 128) over a 1.2 x 2.0 x 0.6 m box:
 * ``torch_chain``: the same folded float32 weights as ``F.linear`` + ``F.softplus`` in float32 on the same GPU, the embedding with
   ``torch.sin`` / ``torch.cos``, in chunks of 256 * 256 * 4 points as ``test_geometry`` does, all 257 columns of the last layer as the
   reference computes them; timed the same way.  ``torch.backends.cuda.matmul.allow_tf32`` is left at its default (off: fp32 products).
+
+``--grad`` adds three legs over the same points in the same chunks, timed the same way and reported under ``"grad"``:
+
+* ``sdf_normal``: ``TemplateField.sdf_normal`` (the fused gradient kernel: value and three tangents, 8 points per weight pass);
+* ``sdf_only``: ``TemplateField.__call__`` on the same chunks (the forward kernel, 32 points per weight pass);
+* ``torch_autograd``: the torch chain above with ``requires_grad_()`` points and ``torch.autograd.grad`` of column 0, TF32 off.
 
 FLOPs: 2 * multiply-adds of the layers the fused kernel runs for an SDF-only request (the last layer counted as ONE column: 256 MACs),
 against the 155 TFLOP/s fp32-matrix peak; the torch chain's rate counts its 257 columns.  Also printed: the largest difference between
@@ -60,6 +66,7 @@ def main():
     ap.add_argument("--res", type=int, nargs=3, default=[256, 256, 128])
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--grad", action="store_true", help="also time sdf_normal against the SDF-only forward and a torch autograd chain")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
@@ -75,21 +82,47 @@ def main():
     axes = [a.to(dev) for a in tf.volume_axes(bounds, res)]
     step = max(1, tf.GRID_CHUNK // (res[1] * res[2]))
 
-    def torch_chain():
-        out = torch.empty(n, dtype=torch.float32, device=dev)
+    def chain(x):
+        e = torch.cat([x] + [fn(x * float(2 ** k)) for k in range(6) for fn in (torch.sin, torch.cos)], -1)
+        h = e
+        for l, (w, b) in enumerate(weights):
+            if l == 4:
+                h = torch.cat([h, e], -1)
+            h = F.linear(h, w, b)
+            if l < len(weights) - 1:
+                h = F.softplus(h, beta=100)
+        return h
+
+    def slabs():
         for x0 in range(0, res[0], step):
             x1 = min(res[0], x0 + step)
-            x = tf.volume_points(axes, x0, x1)
-            e = torch.cat([x] + [fn(x * float(2 ** k)) for k in range(6) for fn in (torch.sin, torch.cos)], -1)
-            h = e
-            for l, (w, b) in enumerate(weights):
-                if l == 4:
-                    h = torch.cat([h, e], -1)
-                h = F.linear(h, w, b)
-                if l < len(weights) - 1:
-                    h = F.softplus(h, beta=100)
-            out[x0 * res[1] * res[2]:x1 * res[1] * res[2]] = -h[:, 0]
+            yield x0 * res[1] * res[2], x1 * res[1] * res[2], tf.volume_points(axes, x0, x1)
+
+    def torch_chain():
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        for p0, p1, x in slabs():
+            out[p0:p1] = -chain(x)[:, 0]
         return out.view(res)
+
+    def sdf_normal():
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        for p0, p1, x in slabs():
+            out[p0:p1] = field.sdf_normal(x)["normal"]
+        return out
+
+    def sdf_only():
+        out = torch.empty((n, 1), dtype=torch.float32, device=dev)
+        for p0, p1, x in slabs():
+            out[p0:p1] = field(x)["sdf"]
+        return out
+
+    def torch_autograd():
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        for p0, p1, x in slabs():
+            x.requires_grad_()
+            s = chain(x)[:, :1]
+            out[p0:p1] = torch.autograd.grad(s, x, torch.ones_like(s))[0]
+        return out
 
     def timed(fn, iters=args.iters):
         fn()
@@ -115,6 +148,16 @@ def main():
            "lds_bytes_per_workgroup": 144896, "workgroups_per_cu": 1, "waves_per_simd": 2,
            "max_abs_difference": float((a - b).abs().max()), "sdf_range": [float(a.min()), float(a.max())],
            "allow_tf32": bool(torch.backends.cuda.matmul.allow_tf32)}
+    if args.grad:
+        legs = {"sdf_normal": sdf_normal, "sdf_only": sdf_only, "torch_autograd": torch_autograd}
+        gruns = [{k: timed(fn) for k, fn in legs.items()} for _ in range(args.runs)]
+        gms = {k: float(np.median([r[k] for r in gruns])) for k in legs}
+        ga, gb = sdf_normal(), torch_autograd()
+        out["grad"] = {"ms": {k: round(v, 3) for k, v in gms.items()}, "ms_runs": [{k: round(v, 3) for k, v in r.items()} for r in gruns],
+                       "sdf_normal_over_sdf_only": round(gms["sdf_normal"] / gms["sdf_only"], 3),
+                       "sdf_normal_over_torch_autograd": round(gms["sdf_normal"] / gms["torch_autograd"], 3),
+                       "tflops_sdf_normal": round(2.0 * 4 * macs_fused * n / (gms["sdf_normal"] * 1e-3) / 1e12, 2),
+                       "max_abs_difference": float((ga - gb).abs().max()), "largest_component": float(gb.abs().max())}
     print(json.dumps(out))
 
 
