@@ -177,6 +177,24 @@ class AgTemplateFieldDesc(ctypes.Structure):  # include/ag_template_field.h
                 + [("geo", AgFieldLayer * AG_FIELD_MAX_LAYERS), ("color", AgFieldLayer * AG_FIELD_MAX_LAYERS)])
 
 
+AG_HAND_MAX_LAYERS = 8
+
+
+class AgHandFusionDesc(ctypes.Structure):     # include/ag_hand_fusion.h
+    _fields_ = [("multires", c_i32), ("n_layers", c_i32), ("width", c_i32 * AG_HAND_MAX_LAYERS)]
+
+
+class AgHandSide(ctypes.Structure):           # include/ag_hand_fusion.h
+    _fields_ = ([(n, c_vp) for n in ("dist2", "face_id", "bary", "vertices", "normals", "cano_vertices", "faces", "blob")]
+                + [("V", c_i32), ("F", c_i32), ("bbox_min", c_f * 3), ("bbox_max", c_f * 3)])
+
+
+class AgHandFieldFuseArgs(ctypes.Structure):  # include/ag_hand_fusion.h
+    _fields_ = ([("N", ctypes.c_int64), ("desc", AgHandFusionDesc), ("centre_y", c_f), ("density_b", c_f)]
+                + [(n, c_vp) for n in ("points", "cano_xyz", "sdf_in", "density_in", "color_in", "sdf", "density", "color")]
+                + [("blob_floats", c_sz), ("left", AgHandSide), ("right", AgHandSide)])
+
+
 # every symbol include/*.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ag_abi_version", ctypes.c_int, []),
@@ -298,6 +316,11 @@ SYMBOLS = [
     ("ag_template_field_forward", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_template_field_grad.h
     ("ag_template_field_sdf_grad", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
+    # include/ag_hand_fusion.h
+    ("ag_hand_field_fuse_args_bytes", c_sz, []),
+    ("ag_hand_fusion_blob_floats", c_sz, [ctypes.POINTER(AgHandFusionDesc)]),
+    ("ag_hand_field_gate", ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_f, c_vp, c_vp]),
+    ("ag_hand_field_fuse", ctypes.c_int, [ctypes.POINTER(AgHandFieldFuseArgs), c_vp]),
     # include/ag_ray_march.h
     ("ag_ray_near_far", ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, ctypes.c_int64, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("ag_ray_sample", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -19,7 +19,7 @@ FAST="-ffp-contract=fast"
 compile() { # src flags
   local src="$1"; shift
   local obj="$OBJ/$(basename "${src%.hip}").o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/ag_common.h" -nt "$obj" ] || [ "$HERE/../../include/ag_raster.h" -nt "$obj" ] || [ "$HERE/../../include/ag_avatar.h" -nt "$obj" ] || [ "$HERE/../../include/ag_styleunet.h" -nt "$obj" ] || [ "$HERE/../../include/ag_conv.h" -nt "$obj" ] || [ "$HERE/../../include/ag_lpips.h" -nt "$obj" ] || [ "$HERE/../../include/ag_smplx.h" -nt "$obj" ] || [ "$HERE/ag_sh.h" -nt "$obj" ] || [ "$HERE/../../include/ag_layers.h" -nt "$obj" ] || [ "$HERE/../../include/ag_optim.h" -nt "$obj" ] || [ "$HERE/../../include/ag_linear.h" -nt "$obj" ] || [ "$HERE/../../include/ag_subject_maps.h" -nt "$obj" ] || [ "$HERE/../../include/ag_metrics.h" -nt "$obj" ] || [ "$HERE/../../include/ag_weight_volume.h" -nt "$obj" ] || [ "$HERE/../../include/ag_targets.h" -nt "$obj" ] || [ "$HERE/../../include/ag_mesh_query.h" -nt "$obj" ] || [ "$HERE/../../include/ag_weight_diffuse.h" -nt "$obj" ] || [ "$HERE/../../include/ag_inverse_skinning.h" -nt "$obj" ] || [ "$HERE/../../include/ag_isosurface.h" -nt "$obj" ] || [ "$HERE/ag_isosurface_table.h" -nt "$obj" ] || [ "$HERE/../../include/ag_template_field.h" -nt "$obj" ] || [ "$HERE/../../include/ag_ray_march.h" -nt "$obj" ] || [ "$HERE/../../include/ag_template_field_grad.h" -nt "$obj" ]; then
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/ag_common.h" -nt "$obj" ] || [ "$HERE/../../include/ag_raster.h" -nt "$obj" ] || [ "$HERE/../../include/ag_avatar.h" -nt "$obj" ] || [ "$HERE/../../include/ag_styleunet.h" -nt "$obj" ] || [ "$HERE/../../include/ag_conv.h" -nt "$obj" ] || [ "$HERE/../../include/ag_lpips.h" -nt "$obj" ] || [ "$HERE/../../include/ag_smplx.h" -nt "$obj" ] || [ "$HERE/ag_sh.h" -nt "$obj" ] || [ "$HERE/../../include/ag_layers.h" -nt "$obj" ] || [ "$HERE/../../include/ag_optim.h" -nt "$obj" ] || [ "$HERE/../../include/ag_linear.h" -nt "$obj" ] || [ "$HERE/../../include/ag_subject_maps.h" -nt "$obj" ] || [ "$HERE/../../include/ag_metrics.h" -nt "$obj" ] || [ "$HERE/../../include/ag_weight_volume.h" -nt "$obj" ] || [ "$HERE/../../include/ag_targets.h" -nt "$obj" ] || [ "$HERE/../../include/ag_mesh_query.h" -nt "$obj" ] || [ "$HERE/../../include/ag_weight_diffuse.h" -nt "$obj" ] || [ "$HERE/../../include/ag_inverse_skinning.h" -nt "$obj" ] || [ "$HERE/../../include/ag_isosurface.h" -nt "$obj" ] || [ "$HERE/ag_isosurface_table.h" -nt "$obj" ] || [ "$HERE/../../include/ag_template_field.h" -nt "$obj" ] || [ "$HERE/../../include/ag_ray_march.h" -nt "$obj" ] || [ "$HERE/../../include/ag_template_field_grad.h" -nt "$obj" ] || [ "$HERE/../../include/ag_hand_fusion.h" -nt "$obj" ]; then
     echo "hipcc $(basename "$src") $*"
     rm -f "$obj"
     local log; log="$(mktemp)"
@@ -66,6 +66,8 @@ compile "$HERE/ag_isosurface.hip" $EXACT &
 compile "$HERE/ag_template_field.hip" $EXACT &
 # near / far, the sample positions and the compositing sums are stated op by op in include/ag_ray_march.h
 compile "$HERE/ag_ray_march.hip" $EXACT &
+# the gates, the interpolation, the hand's signed distance, the blend and the density are stated op by op in include/ag_hand_fusion.h
+compile "$HERE/ag_hand_fusion.hip" $EXACT &
 fail=0
 for job in $(jobs -p); do wait "$job" || fail=1; done
 if [ "$fail" -ne 0 ]; then echo "build.sh: compilation failed" >&2; exit 1; fi

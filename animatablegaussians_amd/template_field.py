@@ -10,8 +10,9 @@ reference template checkpoint becomes the mesh that ``obj_io.save_mesh_ply`` wri
 the reference's ``'normal'``, by a second fused kernel that pushes three tangents through the geometry MLP beside the value
 (``include/ag_template_field_grad.h``); ``eikonal_loss`` is ``main_template.py:53-58`` on it.
 
-NOT here: the hand fusion (``fuse_hands``), any gradient with respect to the weights (template training), any backward.  Ray sampling and
-compositing, the other half of ``TemplateNet.render``, are ``template_render.py``.  Every tensor must be on the GPU; there is no host path
+NOT here: any gradient with respect to the weights (template training), any backward.  Ray sampling and compositing, the other half
+of ``TemplateNet.render``, are ``template_render.py``; the hand fusion (``fuse_hands``, a checkpoint's ``left_hand.*`` / ``right_hand.*``) is
+``hand_fusion.py``.  Every tensor must be on the GPU; there is no host path
 and no PyTorch fallback.
 """
 from __future__ import annotations
@@ -163,7 +164,8 @@ class TemplateField:
                         geo_activation: str = "softplus") -> "TemplateField":
         """``sd``: the reference's ``TemplateNet.state_dict()``.  ``geo_mlp.fc_list.{0..n-1}.0.*`` and ``geo_mlp.fc_list.{n}.*`` carry
         ``weight_g`` / ``weight_v`` (or ``parametrizations.weight.original0`` / ``original1``) and ``bias``; ``tex_mlp.fc_list.*`` plain
-        ``weight`` / ``bias``; ``density_func.beta`` a scalar.  Everything else in ``sd`` (hands, volumes) is ignored."""
+        ``weight`` / ``bias``; ``density_func.beta`` a scalar.  Everything else in ``sd`` is ignored: the volumes, and the two hands' networks, which
+        ``hand_fusion.HandField.from_state_dict`` reads."""
         geo = _mlp(sd, "geo_mlp", must_be_normalised=True)
         color = _mlp(sd, "tex_mlp", must_be_normalised=False)
         beta = _array(sd, "density_func.beta")

@@ -9,7 +9,10 @@ posed space (``inverse_skinning``), the fused field (``template_field.TemplateFi
 ``render_normals`` is the same march with ``compute_grad``: the raw SDF gradient at every sample (``render_output['normal']``,
 ``template.py:380-383``) from ``TemplateField.sdf_normal``, and a composited normal image.
 
-NOT here: the hand fusion (``fuse_hands``), any backward, the training-mode noise on the view directions, the
+``render(..., hands=)`` fuses the hand fields into the body field at every sample (``template.py:365-366``, ``hand_fusion.fuse_hands``) between
+the field and the compositing: what a checkpoint trained with ``with_hand: true`` needs.
+
+NOT here: any backward, the training-mode noise on the view directions, the
 scattering through ``mask_within_patch`` and the dataset-side ray selection of ``nerf_util`` (``get_rays``, ``get_near_far``, patch
 sampling): the caller brings the rays and the box near / far, as the reference's batch does.  Near / far is pinned to the header's
 formulas: the reference's kernel is CUDA and was never run beside this one.  Every tensor must be on the GPU; there is no host path
@@ -228,7 +231,8 @@ def _march_setup(ray_o, ray_d, near, far, space, sampling, live_smpl_v, radius, 
 
 
 def _chunks(setup, space, live, want_dirs):
-    """``(r0, r1, canonical points [(r1 - r0) * S, 3], z [r1 - r0, S], dirs or None)`` of every chunk of rays: sample, then (live) map."""
+    """``(r0, r1, canonical points [(r1 - r0) * S, 3], z [r1 - r0, S], dirs or None, the points as sampled)`` of every chunk of rays:
+    sample, then (live) map."""
     o, d, near, far, t, u, mask, chunk_size, _ = setup
     if space == "live":
         from .inverse_skinning import transform_live2cano
@@ -236,16 +240,16 @@ def _chunks(setup, space, live, want_dirs):
         r1 = min(o.shape[0], r0 + chunk_size)
         pts, z, dirs = _sample(o[r0:r1], d[r0:r1], near[r0:r1], far[r0:r1], t, None if u is None else u[r0:r1], None if mask is None else mask[r0:r1],
                                want_dirs)
-        pts = pts.view(-1, 3)
+        pts = sampled = pts.view(-1, 3)
         if space == "live":
             pts = transform_live2cano(pts[None], **live)[0][0]
-        yield r0, r1, pts, z, dirs
+        yield r0, r1, pts, z, dirs, sampled
 
 
 def render(field, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.Tensor, far: torch.Tensor, *, space: str = "cano", sampling: str = "smpl",
            live_smpl_v: Optional[torch.Tensor] = None, radius: float = 0.1, dist: Optional[torch.Tensor] = None,
            near_sur_dist: Optional[float] = None, n_samples: int = 64, u: Optional[torch.Tensor] = None, chunk_size: int = 4096,
-           white_bkgd: bool = False, live: Optional[dict] = None, want=("rgb_map", "acc_map")):
+           white_bkgd: bool = False, live: Optional[dict] = None, want=("rgb_map", "acc_map"), hands: Optional[dict] = None):
     """``TemplateNet.render`` in eval mode for one batch element: rays ``ray_o`` / ``ray_d`` [R, 3] (or [1, R, 3]) with the box ``near`` /
     ``far`` [R] (or [1, R]) through ``field`` (a ``TemplateField``) -> dict of ``rgb_map`` [R, 3], ``acc_map`` [R] and, when named in
     ``want``, ``depth_map``, ``disp_map``, ``weights`` [R, S]; a leading 1 of the rays is kept in the outputs.
@@ -259,20 +263,37 @@ def render(field, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.Tensor, 
     ``inverse_skinning.transform_live2cano`` by name (``cano2live_jnt_mats``, ``volume``, ``live_mesh_v``, ``live_mesh_f``,
     ``live_mesh_lbs`` and optionally ``near_thres``, ``use_root_finding``, ``with_hand`` ..).  The rays are processed ``chunk_size`` at
     a time: sample, map, field, composite straight into the outputs; nothing depends on ``chunk_size``, bit for bit.  A field without
-    a colour MLP renders everything but ``rgb_map``."""
+    a colour MLP renders everything but ``rgb_map``.
+
+    ``hands`` (the reference's ``with_hand``): ``dict(left=dict(v=, n=, f=, cano_v=), right=dict(...), left_field=, right_field=,
+    cano_smpl_center=)`` and optionally ``hand_pose`` [45] and ``compact``: the two hand meshes with ``v`` / ``n`` in the space the rays
+    are in (``hand_fusion.hand_meshes`` of the posed vertices for ``space="live"``, of the canonical ones for ``"cano"``) and ``cano_v``
+    in canonical space, the two ``HandField`` and the centre.  Every chunk then goes through ``hand_fusion.fuse_hands`` between the
+    field and the composite.  Without ``hands`` nothing of it runs and the outputs are what they were, bit for bit."""
     from .template_field import TemplateField
     if not isinstance(field, TemplateField):
         raise ValueError("field must be a TemplateField")
     want = _want(want)
     if "rgb_map" in want and not field.color:
         raise ValueError("this field has no colour MLP: rgb_map cannot be rendered")
+    if hands is not None:
+        required = {"left", "right", "left_field", "right_field", "cano_smpl_center"}
+        if not isinstance(hands, dict) or not required <= set(hands) or not set(hands) <= required | {"hand_pose", "compact"}:
+            raise ValueError("hands must be dict(left=, right=, left_field=, right_field=, cano_smpl_center=[, hand_pose=, compact=])")
+        from . import hand_fusion
+        hand_pose = hand_fusion.check_fields(hands["left_field"], hands["right_field"], hands.get("hand_pose"))      # no launch: a refusal here leaves nothing behind
     setup = _march_setup(ray_o, ray_d, near, far, space, sampling, live_smpl_v, radius, dist, near_sur_dist, n_samples, u, chunk_size, live)
     o, t, batched = setup[0], setup[4], setup[8]
+    if hands is not None:                           # the meshes: checked and their boxes reduced on the device, once, after near / far
+        prepared = hand_fusion.PreparedHands(hands, o.device)
     out = _outputs(want, o.shape[0], t.shape[0], o.device)
     field_want = ("sdf", "density", "color") if "rgb_map" in want else ("sdf", "density")
     use_dirs = bool(field.use_viewdir) and "rgb_map" in want
-    for r0, r1, pts, z, dirs in _chunks(setup, space, live, use_dirs):
+    for r0, r1, pts, z, dirs, sampled in _chunks(setup, space, live, use_dirs):
         ret = field(pts, dirs.view(-1, 3) if use_dirs else None, want=field_want)
+        if hands is not None:
+            ret = hand_fusion.fuse_hands(ret, sampled, prepared, hands["left_field"], hands["right_field"], cano_smpl_center=hands["cano_smpl_center"],
+                                         density_b=field.density_b, hand_pose=hand_pose, compact=hands.get("compact", True))
         _composite_into(ret["density"], ret.get("color"), z, white_bkgd, {k: v[r0:r1] for k, v in out.items()})
     out = {k: v for k, v in out.items() if k in want}
     return {k: v[None] for k, v in out.items()} if batched else out
@@ -304,7 +325,7 @@ def render_normals(field, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.
     R, S, dev = o.shape[0], t.shape[0], o.device
     out = _outputs(tuple(k for k in want if k in OUTPUTS) + (("rgb_map",) if "normal_map" in want else ()), R, S, dev)
     normal = torch.empty((R, S, 3), dtype=torch.float32, device=dev) if "normal" in want else None
-    for r0, r1, pts, z, _ in _chunks(setup, space, live, False):
+    for r0, r1, pts, z, _, _ in _chunks(setup, space, live, False):
         ret = field.sdf_normal(pts, want=("sdf", "normal", "density"))
         n = ret["normal"]
         if normal is not None:
