@@ -33,20 +33,6 @@
 
 namespace ag {
 
-struct BlendFwdParams {
-    int W, H, gx, T;
-    const uint2* __restrict__ ranges;
-    const uint32_t* __restrict__ point_list;
-    const GaussRec* __restrict__ rec;
-    const uint4* __restrict__ tile_order;
-    const uint32_t* __restrict__ counts;   // [0] instances, [1] non-empty tiles
-    const float* __restrict__ bg;
-    float* __restrict__ out_color;
-    float* __restrict__ out_depth;
-    float* __restrict__ out_alpha;
-    uint32_t* __restrict__ n_contrib;
-};
-
 __device__ __forceinline__ float row_lane15(float v)   // row_newbcast:15: every lane receives lane 15 of its 16-lane row
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x15f, 0xf, 0xf, true));
@@ -90,7 +76,36 @@ extern "C" int ag_debug_fwd_stats(unsigned long long* out)
 #ifndef AG_FWD_WAVES_PER_SIMD
 #define AG_FWD_WAVES_PER_SIMD 8      // <= 64 VGPRs: four resident workgroups per CU (71 VGPRs without the bound: 58.8 us against 52.2, profiles/ab_fwd.sh)
 #endif
-__global__ void __launch_bounds__(kBlendThreads, AG_FWD_WAVES_PER_SIMD) blend_forward_kernel(BlendFwdParams p)
+// Background of one empty tile: stores only (bg lives in scalar registers), 256 of the 512 threads.
+__device__ __forceinline__ void fill_empty_tile(int tile, int tid, int W, int H, int gx, float bg0, float bg1, float bg2,
+                                                float* __restrict__ out_color, float* __restrict__ out_depth, float* __restrict__ out_alpha,
+                                                uint32_t* __restrict__ n_contrib)
+{
+    const int px = (tile % gx) * kTileX + (tid & 15), py = (tile / gx) * kTileY + (tid >> 4);
+    if (tid < kTileX * kTileY && px < W && py < H) {
+        const int pix = W * py + px;
+        const size_t HW = (size_t)W * H;
+        n_contrib[pix] = 0;
+        out_color[pix] = bg0;
+        out_color[HW + pix] = bg1;
+        out_color[2 * HW + pix] = bg2;
+        out_alpha[pix] = 0.f;
+        out_depth[pix] = 0.f;
+    }
+}
+
+// The pointers are separate `const T* __restrict__` PARAMETERS, not members of a by-value struct: __restrict__ on the members of a struct
+// passed by value is ignored, so the compiler had to assume that bg and tile_order alias the output images and reloaded them (vector
+// load + wait, which on this part also waits for the store in front of it) after every store.  As parameters, bg, counts, the item headers
+// and the empty tiles' ids all come through the scalar path (s_load into SGPRs, lgkmcnt): no wait of theirs touches vmcnt, and the six
+// stores of a pixel go out back to back.  Listings, the placements of the empty-tile fill that were measured and the figures:
+// profiles/blend_forward_waits.md.
+__global__ void __launch_bounds__(kBlendThreads, AG_FWD_WAVES_PER_SIMD)
+blend_forward_kernel(int W, int H, int gx, int n_tiles, const uint32_t* __restrict__ point_list, const GaussRec* __restrict__ rec,
+                     const uint4* __restrict__ tile_order,
+                     const uint32_t* __restrict__ counts,   // [0] instances, [1] non-empty tiles
+                     const float* __restrict__ bg, float* __restrict__ out_color, float* __restrict__ out_depth,
+                     float* __restrict__ out_alpha, uint32_t* __restrict__ n_contrib)
 {
     constexpr int NW = kBlendThreads / 64;
     __shared__ float4 s_rec[kChunk * 3];
@@ -100,44 +115,36 @@ __global__ void __launch_bounds__(kBlendThreads, AG_FWD_WAVES_PER_SIMD) blend_fo
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int row = lane >> 4, e = lane & 15;
-    const uint32_t n_active = p.counts[1];
-
-    // Empty tiles (the tail of the work order) only need their background: static share.
-    for (uint32_t t = n_active + blockIdx.x; t < (uint32_t)p.T; t += gridDim.x) {
-        const int tile = (int)p.tile_order[t].x;
-        const int px = (tile % p.gx) * kTileX + (tid & 15), py = (tile / p.gx) * kTileY + (tid >> 4);
-        if (tid < kTileX * kTileY && px < p.W && py < p.H) {
-            const int pix = p.W * py + px;
-            const size_t HW = (size_t)p.W * p.H;
-            p.n_contrib[pix] = 0;
-            p.out_color[pix] = p.bg[0];
-            p.out_color[HW + pix] = p.bg[1];
-            p.out_color[2 * HW + pix] = p.bg[2];
-            p.out_alpha[pix] = 0.f;
-            p.out_depth[pix] = 0.f;
-        }
-    }
+    // read once per launch, above the first store: three scalar registers for the whole kernel
+    const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
+    const uint32_t n_active = counts[1];
 
     // Static work assignment (see ItemIter); the descriptor of item i+1 is fetched while item i is blended.
     ItemIter<kRegionsPerTile> it(blockIdx.x, gridDim.x, n_active);
     uint32_t tr, rg;
     bool have = it.next(tr, rg);
-    uint4 hdr = make_uint4(0u, 0u, 0u, 0u);
-    if (have) { hdr = p.tile_order[tr]; hdr.w = rg; }
+    // every rank below n_tiles holds a valid descriptor (the empty tiles are the tail of the order): the load is unconditional
+    uint4 hdr = tile_order[tr < (uint32_t)n_tiles ? tr : 0u];
+    hdr.w = rg;
+
+    // Empty tiles (the tail of the work order) only need their background: static share.  The rank's tile id is fetched together with the
+    // item header and the stores go out while the item's own loads are in flight (one tile per item); what is left follows the item loop.
+    uint32_t t_fill = n_active + blockIdx.x;
+    int fill_tile = (int)tile_order[t_fill < (uint32_t)n_tiles ? t_fill : 0u].x;
 
     while (have) {
         uint32_t tr_n, rg_n;
         const bool have_n = it.next(tr_n, rg_n);
-        uint4 hdr_n = make_uint4(0u, 0u, 0u, 0u);
-        if (have_n) { hdr_n = p.tile_order[tr_n]; hdr_n.w = rg_n; }
+        uint4 hdr_n = tile_order[tr_n < (uint32_t)n_tiles ? tr_n : 0u];
+        hdr_n.w = rg_n;
 
         const int tile = (int)hdr.x, reg = (int)hdr.w;
         const uint2 range = make_uint2(hdr.y, hdr.z);
-        const int tile_x = tile % p.gx, tile_y = tile / p.gx;
+        const int tile_x = tile % gx, tile_y = tile / gx;
         const int rx0 = tile_x * kTileX + (reg & 1) * kRegW, ry0 = tile_y * kTileY + (reg >> 1) * kRegH;
         // the wave's 4 pixels form a 2x2 block (better coherence of the per-wave early-outs than a 4x1 strip)
         const int px = rx0 + (wave & 3) * 2 + (row & 1), py = ry0 + (wave >> 2) * 2 + (row >> 1);
-        const bool inside = px < p.W && py < p.H;
+        const bool inside = px < W && py < H;
         const float pxf = (float)px, pyf = (float)py;
         const float qx0f = (float)rx0, qy0f = (float)ry0, qx1f = (float)(rx0 + kRegW - 1), qy1f = (float)(ry0 + kRegH - 1);
 
@@ -154,10 +161,17 @@ __global__ void __launch_bounds__(kBlendThreads, AG_FWD_WAVES_PER_SIMD) blend_fo
         float4 r0, r1, r2;
         {
             const uint32_t k0 = range.x + tid, k1 = k0 + kChunk;
-            const uint32_t id0 = p.point_list[k0 < range.y ? k0 : range.x];
-            id_next = p.point_list[k1 < range.y ? k1 : range.x];
-            const float4* src = reinterpret_cast<const float4*>(p.rec + id0);
+            const uint32_t id0 = point_list[k0 < range.y ? k0 : range.x];
+            id_next = point_list[k1 < range.y ? k1 : range.x];
+            const float4* src = reinterpret_cast<const float4*>(rec + id0);
             r0 = src[0]; r1 = src[1]; r2 = src[2];
+        }
+        // one empty tile's background behind the item's loads: the stores need no answer, and the next rank's id is back long before the
+        // next item asks for it
+        if (t_fill < (uint32_t)n_tiles) {
+            fill_empty_tile(fill_tile, tid, W, H, gx, bg0, bg1, bg2, out_color, out_depth, out_alpha, n_contrib);
+            t_fill += gridDim.x;
+            fill_tile = (int)tile_order[t_fill < (uint32_t)n_tiles ? t_fill : 0u].x;
         }
         // cull of chunk 0: the cut-off disc.  (The backward's exact quadratic-form cull was measured here and NOT kept: fewer survivors,
         // 62.3 us against 47.2 -- profiles/r06_fwd_exact_cull.txt.)
@@ -201,10 +215,10 @@ __global__ void __launch_bounds__(kBlendThreads, AG_FWD_WAVES_PER_SIMD) blend_fo
             // issue the gathers of chunk c+1 and the index loads of chunk c+2; both are consumed after the blend
             const uint32_t kn = k + kChunk, knn = kn + kChunk;
             {
-                const float4* src = reinterpret_cast<const float4*>(p.rec + id_next);
+                const float4* src = reinterpret_cast<const float4*>(rec + id_next);
                 r0 = src[0]; r1 = src[1]; r2 = src[2];
             }
-            id_next = p.point_list[knn < range.y ? knn : range.x];
+            id_next = point_list[knn < range.y ? knn : range.x];
             lds_barrier();
 
             // ---- second cull, per wave: a splat that reaches the 8x4 region reaches on average 40 % of its eight 2x2 blocks.
@@ -315,51 +329,55 @@ __global__ void __launch_bounds__(kBlendThreads, AG_FWD_WAVES_PER_SIMD) blend_fo
         AG_ROW_SUM_STEP(1) AG_ROW_SUM_STEP(2) AG_ROW_SUM_STEP(4) AG_ROW_SUM_STEP(8)
 #undef AG_ROW_SUM_STEP
         if (inside && e == 15) {
-            const int pix = p.W * py + px;
-            const size_t HW = (size_t)p.W * p.H;
-            p.n_contrib[pix] = lm;
-            p.out_color[pix] = Cr + T * p.bg[0];
-            p.out_color[HW + pix] = Cg + T * p.bg[1];
-            p.out_color[2 * HW + pix] = Cb + T * p.bg[2];
-            p.out_alpha[pix] = Ws;
-            p.out_depth[pix] = Dd;
+            const int pix = W * py + px;
+            const size_t HW = (size_t)W * H;
+            n_contrib[pix] = lm;
+            out_color[pix] = Cr + T * bg0;
+            out_color[HW + pix] = Cg + T * bg1;
+            out_color[2 * HW + pix] = Cb + T * bg2;
+            out_alpha[pix] = Ws;
+            out_depth[pix] = Dd;
         }
         lds_barrier();   // s_rec / counters reusable
         hdr = hdr_n;
         have = have_n;
     }
+
+    // the empty tiles that no item carried: workgroups without an item, and images with more empty tiles than items
+    while (t_fill < (uint32_t)n_tiles) {
+        fill_empty_tile(fill_tile, tid, W, H, gx, bg0, bg1, bg2, out_color, out_depth, out_alpha, n_contrib);
+        t_fill += gridDim.x;
+        fill_tile = (int)tile_order[t_fill < (uint32_t)n_tiles ? t_fill : 0u].x;
+    }
 }
 
 int launch_blend_forward(const AgRasterForwardArgs& a, int R, hipStream_t s)
 {
-    BlendFwdParams p;
-    p.W = a.W; p.H = a.H;
-    p.gx = (a.W + kTileX - 1) / kTileX;
-    const int gy = (a.H + kTileY - 1) / kTileY;
-    p.T = p.gx * gy;
+    const int gx = (a.W + kTileX - 1) / kTileX, gy = (a.H + kTileY - 1) / kTileY;
+    const int n_tiles = gx * gy;
     char* gb = aligned_base(a.geom_buffer);
     char* ib = aligned_base(a.image_buffer);
     GeomLayout gl((size_t)a.P);
     ImageLayout il((size_t)a.W, (size_t)a.H);
-    p.ranges = reinterpret_cast<const uint2*>(ib + il.ranges);
-    p.rec = reinterpret_cast<const GaussRec*>(gb + gl.rec);
+    const GaussRec* rec = reinterpret_cast<const GaussRec*>(gb + gl.rec);
+    const uint32_t* point_list = nullptr;  // R == 0: every range is (0,0), never dereferenced
     if (R > 0) {
         BinLayout bl((size_t)R);
-        p.point_list = reinterpret_cast<const uint32_t*>(aligned_base(a.binning_buffer) + bl.point_list);
-    } else {
-        p.point_list = nullptr;  // every range is (0,0): never dereferenced
+        point_list = reinterpret_cast<const uint32_t*>(aligned_base(a.binning_buffer) + bl.point_list);
     }
-    p.tile_order = reinterpret_cast<const uint4*>(ib + il.tile_order);
-    p.counts = reinterpret_cast<const uint32_t*>(ib + il.num_rendered);
-    p.bg = a.bg;
-    p.out_color = a.out_color; p.out_depth = a.out_depth; p.out_alpha = a.out_alpha;
-    p.n_contrib = reinterpret_cast<uint32_t*>(ib + il.n_contrib);
+    const uint4* tile_order = reinterpret_cast<const uint4*>(ib + il.tile_order);
+    const uint32_t* counts = reinterpret_cast<const uint32_t*>(ib + il.num_rendered);
+    uint32_t* n_contrib = reinterpret_cast<uint32_t*>(ib + il.n_contrib);
     // up to kBlendGrid (6144) workgroups, of which 1024 (4 per CU) are resident: one item each on avatar views (~5000 region items), the
     // longest lists first, and the hardware dispatcher starts the rest wherever a slot frees up first -- load balancing without atomics
     // (see kBlendGrid in ag_common.h for the measurements); beyond that the static rule deals several items per workgroup.
-    const long long items = (long long)p.T * kRegionsPerTile;
+    const long long items = (long long)n_tiles * kRegionsPerTile;
     const int grid = (int)(items < kBlendGrid ? items : kBlendGrid);
-    { ProfScope ps(AG_K_BLEND_FORWARD, s); hipLaunchKernelGGL(blend_forward_kernel, dim3(grid), dim3(kBlendThreads), 0, s, p); }
+    {
+        ProfScope ps(AG_K_BLEND_FORWARD, s);
+        hipLaunchKernelGGL(blend_forward_kernel, dim3(grid), dim3(kBlendThreads), 0, s, a.W, a.H, gx, n_tiles, point_list, rec, tile_order,
+                           counts, a.bg, a.out_color, a.out_depth, a.out_alpha, n_contrib);
+    }
     return check_hip(hipGetLastError(), "blend_forward_kernel");
 }
 
