@@ -6,17 +6,15 @@
 //      into the hand's layer-0 input row in LDS, the raw weight and sdf_h into s_w / s_sdf;
 //   B  all threads: the sin / cos columns of both hands' embeddings from the x just written, zeros in the padding columns;
 //   C  the MLP, waves 0-1 on the left hand and waves 2-3 on the right: a layer is D[point][n] = bias[n] + sum_k U[point][k] W[n][k] on
-//      v_mfma_f32_32x32x2_f32 with the operand reads, the packed blob and the k order of csrc/ag_template_field.hip; a hand's two
+//      v_mfma_f32_32x32x2_f32 with the operand reads, the packed blob and the k order of csrc/ag_mlp_tile.h; a hand's two
 //      waves take the layer's 32-column tiles alternately; the last layer writes sigmoid to s_col;
 //   D  threads 0 .. 31, one per point: normalise the weights, blend, density, write (or copy the body's values).
 // A tile in which no (hand, point) has weight skips B and C.
 // Weights come from L2 (167 KB for both reference nets); nothing but the per-point inputs and the outputs touches HBM.
 //
 // Compiled WITHOUT fp contraction (build.sh EXACT): the header states everything but the product sums op by op.
-#include "ag_common.h"
+#include "ag_mlp_tile.h"
 #include "../../include/ag_hand_fusion.h"
-
-#include <cmath>
 
 namespace ag {
 namespace handfuse {
@@ -58,9 +56,7 @@ struct Params {
     Side side[2];
 };
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+using namespace ag::mlp;
 
 __device__ __forceinline__ float norm_axis(float x, float mn, float mx) { return (2.0f * (x - 0.5f * (mx + mn))) / (mx - mn); }
 
@@ -73,15 +69,6 @@ __device__ __forceinline__ void gates(float cx, float cy, float lmn, float lmx, 
 }
 
 __device__ __forceinline__ float dot3(float x0, float x1, float x2, float y0, float y1, float y2) { return (x0 * y0 + x1 * y1) + x2 * y2; }
-
-__device__ __forceinline__ f32x16 mac8(f32x16 acc, const float4 a, const float4 w)
-{
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, w.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, w.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, w.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, w.w, acc, 0, 0, 0);
-    return acc;
-}
 
 __global__ void __launch_bounds__(256) hand_gate_kernel(const float* __restrict__ cano_xyz, long long N, float lmn, float lmx, float rmn, float rmx,
                                                         float centre_y, unsigned char* __restrict__ active)
@@ -191,14 +178,10 @@ __global__ void __launch_bounds__(kThreads) hand_fuse_kernel(Plan plan, Params a
                     f32x16 acc;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[r] = bias;
-                    const float4* w = reinterpret_cast<const float4*>(blob + lp.w_off) + (size_t)h * lp.Np + n;
-                    const float* u = in + i * kStride + 4 * h;
-                    const int groups = lp.Kp >> 3;
-                    for (int g = 0; g < groups; ++g) acc = mac8(acc, *reinterpret_cast<const float4*>(u + 8 * g), w[g * wstep]);
-                    // C/D map of the 32x32 forms: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+                    acc = products(acc, in + i * kStride + 4 * h, weights(blob, lp.w_off, lp.Np, n, h), wstep, lp.Kp >> 3);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int row = cd_row(r, h);
                         if (last) {
                             if (i < 3) s_col[(hand_w * kPoints + row) * 4 + i] = sigmoid(acc[r]);
                         } else {
@@ -238,10 +221,7 @@ __global__ void __launch_bounds__(kThreads) hand_fuse_kernel(Plan plan, Params a
                     for (int c = 0; c < 3; ++c) cb[c] = a.color_in[(size_t)n * 3 + c];
                 }
                 a.sdf[n] = sdf;
-                const float raw = -sdf;
-                const float sgn = raw > 0.0f ? 1.0f : (raw < 0.0f ? -1.0f : 0.0f);
-                const float em = expm1f(-fabsf(raw) / a.b);
-                a.density[n] = alpha * (0.5f + (0.5f * sgn) * em);
+                a.density[n] = sdf_density(-sdf, a.b, alpha);
                 if (want_color) {
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
@@ -255,9 +235,6 @@ __global__ void __launch_bounds__(kThreads) hand_fuse_kernel(Plan plan, Params a
         __syncthreads();      // s_w / s_col / the input rows are rewritten by the next tile
     }
 }
-
-inline int pad8(int v) { return (v + 7) / 8 * 8; }
-inline int pad32(int v) { return (v + 31) / 32 * 32; }
 
 // Validates `d` against the limits of the header and lays one hand's blob out; returns its floats through `total`.
 int make_plan(const AgHandFusionDesc* d, Plan& plan, size_t& total)
@@ -297,24 +274,21 @@ int make_plan(const AgHandFusionDesc* d, Plan& plan, size_t& total)
     return AG_OK;
 }
 
-int fill_side(const AgHandSide& s, const char* name, bool want_color, Side& o)
+int fill_side(const AgHandSide& s, const char* what, bool want_color, Side& o)
 {
-    if (s.V < 0 || s.F < 0) { set_error("hand fusion: %s hand: V = %d and F = %d must not be negative", name, s.V, s.F); return AG_ERR_INVALID_ARGUMENT; }
+    if (s.V < 0 || s.F < 0) { set_error("%s: V = %d and F = %d must not be negative", what, s.V, s.F); return AG_ERR_INVALID_ARGUMENT; }
     for (int c = 0; c < 3; ++c) {
         if (!std::isfinite(s.bbox_min[c]) || !std::isfinite(s.bbox_max[c]) || !(s.bbox_max[c] > s.bbox_min[c])) {
-            set_error("hand fusion: %s hand: the canonical box [%g, %g] of axis %d is empty or not finite", name, (double)s.bbox_min[c], (double)s.bbox_max[c], c);
+            set_error("%s: the canonical box [%g, %g] of axis %d is empty or not finite", what, (double)s.bbox_min[c], (double)s.bbox_max[c], c);
             return AG_ERR_INVALID_ARGUMENT;
         }
     }
-    if (!s.face_id) { set_error("hand fusion: %s hand: face_id is NULL", name); return AG_ERR_INVALID_ARGUMENT; }
+    if (!s.face_id) { set_error("%s: face_id is NULL", what); return AG_ERR_INVALID_ARGUMENT; }
     if (s.F > 0 && (!s.dist2 || !s.bary || !s.vertices || !s.normals || !s.cano_vertices || !s.faces)) {
-        set_error("hand fusion: %s hand: null pointer among dist2, bary, vertices, normals, cano_vertices, faces", name);
+        set_error("%s: null pointer among dist2, bary, vertices, normals, cano_vertices, faces", what);
         return AG_ERR_INVALID_ARGUMENT;
     }
-    if (want_color) {
-        if (!s.blob) { set_error("hand fusion: %s hand: blob is NULL", name); return AG_ERR_INVALID_ARGUMENT; }
-        if (reinterpret_cast<uintptr_t>(s.blob) % 16 != 0) { set_error("hand fusion: %s hand: the blob is not 16-byte aligned", name); return AG_ERR_INVALID_ARGUMENT; }
-    }
+    if (int rc = want_color ? check_blob(what, s.blob) : AG_OK) return rc;
     o.dist2 = s.dist2; o.face_id = s.face_id; o.bary = s.bary; o.vertices = s.vertices; o.normals = s.normals; o.cano_vertices = s.cano_vertices;
     o.faces = s.faces; o.blob = s.blob;
     o.V = s.V; o.F = s.F;
@@ -369,8 +343,7 @@ extern "C" int ag_hand_field_fuse(const AgHandFieldFuseArgs* args, void* stream)
     size_t total = 0;
     if (int rc = make_plan(&args->desc, plan, total)) return rc;
     const AgHandFieldFuseArgs& g = *args;
-    if (g.N < 0 || g.N >= (1ll << 31)) { set_error("hand fusion: N = %lld must be 0 .. 2^31 - 1", (long long)g.N); return AG_ERR_INVALID_ARGUMENT; }
-    if (g.blob_floats != total) { set_error("hand fusion: blobs of %zu floats, %zu expected for this table", g.blob_floats, total); return AG_ERR_INVALID_ARGUMENT; }
+    if (int rc = check_sizes("hand fusion", g.N, INT32_MAX, g.blob_floats, total)) return rc;
     if (!(g.density_b > 0.f) || !std::isfinite(g.density_b) || !std::isfinite(g.centre_y)) {
         set_error("hand fusion: density_b = %g must be finite and positive and centre_y = %g finite", (double)g.density_b, (double)g.centre_y);
         return AG_ERR_INVALID_ARGUMENT;
@@ -378,8 +351,8 @@ extern "C" int ag_hand_field_fuse(const AgHandFieldFuseArgs* args, void* stream)
     if ((g.color == nullptr) != (g.color_in == nullptr)) { set_error("hand fusion: color and color_in must both be given or both be NULL"); return AG_ERR_INVALID_ARGUMENT; }
     Params p{};
     const bool want_color = g.color != nullptr;
-    if (int rc = fill_side(g.left, "left", want_color, p.side[0])) return rc;
-    if (int rc = fill_side(g.right, "right", want_color, p.side[1])) return rc;
+    if (int rc = fill_side(g.left, "hand fusion: left hand", want_color, p.side[0])) return rc;
+    if (int rc = fill_side(g.right, "hand fusion: right hand", want_color, p.side[1])) return rc;
     if (g.N == 0) return AG_OK;
     if (!g.points || !g.cano_xyz || !g.sdf_in || !g.density_in || !g.sdf || !g.density) { set_error("null pointer in ag_hand_field_fuse"); return AG_ERR_INVALID_ARGUMENT; }
     p.N = g.N;
@@ -388,11 +361,8 @@ extern "C" int ag_hand_field_fuse(const AgHandFieldFuseArgs* args, void* stream)
     p.b = g.density_b;
     p.points = g.points; p.cano_xyz = g.cano_xyz; p.sdf_in = g.sdf_in; p.density_in = g.density_in; p.color_in = g.color_in;
     p.sdf = g.sdf; p.density = g.density; p.color = g.color;
-    int dev = 0, cus = 0;
-    if (int rc = check_hip(hipGetDevice(&dev), "hand fusion hipGetDevice")) return rc;
-    if (int rc = check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "hand fusion CU count")) return rc;
-    const long long cap = 16ll * cus;                                          // four workgroups fit a CU (LDS); the rest is the grid-stride loop
-    const long long grid = p.n_tiles < cap ? p.n_tiles : cap;
-    hipLaunchKernelGGL(hand_fuse_kernel, dim3((unsigned)grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), plan, p);
+    unsigned grid = 0;                                                         // four workgroups fit a CU (LDS); the rest is the grid-stride loop
+    if (int rc = persistent_grid(p.n_tiles, 16, "hand fusion device query", &grid)) return rc;
+    hipLaunchKernelGGL(hand_fuse_kernel, dim3(grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), plan, p);
     return check_hip(hipGetLastError(), "hand_fuse_kernel");
 }

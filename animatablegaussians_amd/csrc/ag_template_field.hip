@@ -1,5 +1,6 @@
-// The template stage's field (include/ag_template_field.h): embedding -> geometry MLP -> colour MLP -> density, one fused forward kernel;
-// below it the SDF with its gradient (include/ag_template_field_grad.h), a second kernel of the same shape.
+// The template stage's field (include/ag_template_field.h): embedding -> geometry MLP -> colour MLP -> density, one fused forward kernel,
+// field_kernel<false>; the SDF with its gradient (include/ag_template_field_grad.h) is field_kernel<true>, the same tile, layer and
+// product loops with its own embedding, accumulator start and epilogue.
 //
 // Shape.  A workgroup of 8 waves owns a tile of kPoints = 32 points and keeps it in LDS from the embedding to the outputs:
 //   emb   [32][kEmbStride]   the positional embedding (columns 0 .. 63) and the view embedding (64 .. 95), padding columns zero;
@@ -8,18 +9,17 @@
 // tile of outputs the columns of B, one wave per tile (tile t of a layer goes to wave (t - first tile) mod 8).  Lane l (i = l & 31,
 // h = l >> 5) feeds A[i][k] and B[k][i] for one k per instruction; for a group of 8 consecutive k it reads A as ONE 16-byte LDS read
 // (k0 + 4 h .. k0 + 4 h + 3 of point i) and B as ONE 16-byte global read of the packed blob ([k / 4][n][4], so a wave reads 2 x 512
-// contiguous bytes), then issues 4 MFMAs: the k order inside a group is k0, k0+4, k0+1, k0+5, ... as the header states.  The accumulator
+// contiguous bytes), then issues 4 MFMAs: the k order inside a group is k0, k0+4, k0+1, k0+5, ... as the header states.  These reads, the
+// order and the C/D row map are csrc/ag_mlp_tile.h's, shared with the hand fusion.  The accumulator
 // starts from the bias.  Weights come from L2 (2.8 MB for both reference networks); nothing but xyz / viewdirs and the outputs touches HBM.
 //
 // The SDF column sits alone in the last 32-column tile of the last geometry layer (the blob's column order), so a request without
 // colour computes that one tile and stops; with colour the same tile is computed by the same code, hence bit-identical.
 //
 // Compiled WITHOUT fp contraction (build.sh EXACT): the header states the embedding, the activations and the density op by op.
-#include "ag_common.h"
+#include "ag_mlp_tile.h"
 #include "../../include/ag_template_field.h"
 #include "../../include/ag_template_field_grad.h"
-
-#include <cmath>
 
 namespace ag {
 namespace field {
@@ -56,7 +56,7 @@ struct Plan {
     LayerPlan layer[2 * AG_FIELD_MAX_LAYERS];
 };
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace ag::mlp;
 
 __device__ __forceinline__ float activate(float x, int act, float beta)
 {
@@ -65,7 +65,7 @@ __device__ __forceinline__ float activate(float x, int act, float beta)
         return bx > 20.0f ? x : log1pf(expf(bx)) / beta;
     }
     if (act == AG_FIELD_ACT_RELU) return x > 0.0f ? x : 0.0f;
-    if (act == AG_FIELD_ACT_SIGMOID) return 1.0f / (1.0f + expf(-x));
+    if (act == AG_FIELD_ACT_SIGMOID) return sigmoid(x);
     return x;
 }
 
@@ -90,100 +90,12 @@ __device__ __forceinline__ void embed_tile(float* emb, int off, int L, const flo
     for (int e = threadIdx.x; e < kPoints * pad; e += kThreads) emb[(e / pad) * kEmbStride + off + cols + e % pad] = 0.0f;
 }
 
-__device__ __forceinline__ f32x16 mac8(f32x16 acc, const float4 a, const float4 w)
-{
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, w.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, w.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, w.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, w.w, acc, 0, 0, 0);
-    return acc;
-}
-
-__global__ void __launch_bounds__(kThreads) template_field_kernel(Plan plan, const float* __restrict__ blob, const float* __restrict__ xyz,
-                                                                  const float* __restrict__ viewdirs, long long N, long long n_tiles,
-                                                                  float* __restrict__ sdf, float* __restrict__ density, float* __restrict__ color)
-{
-    __shared__ __attribute__((aligned(16))) float act_lds[2 * kPoints * kActStride];
-    __shared__ __attribute__((aligned(16))) float emb[kPoints * kEmbStride];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    const bool want_view = plan.Lv >= 0;                // some layer that runs concatenates the view embedding
-    const float alpha = 1.0f / plan.b;
-
-    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const long long p0 = tile * kPoints;
-        embed_tile(emb, 0, plan.L, xyz, p0, N);
-        if (want_view) embed_tile(emb, kEmbPos, plan.Lv, viewdirs, p0, N);
-        __syncthreads();
-        float* in = act_lds + kPoints * kActStride;
-        float* out = act_lds;
-        for (int l = 0; l < plan.n_layers; ++l) {
-            const LayerPlan lp = plan.layer[l];
-            const int n_col_tiles = lp.Np >> 5;
-            const size_t wstep = 2 * (size_t)lp.Np;                    // float4s between two groups of 8 k
-            for (int t = lp.first_tile + wave; t < n_col_tiles; t += kWaves) {
-                const int n = t * 32 + i;
-                const float bias = blob[lp.b_off + n];
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = bias;
-                const float4* w = reinterpret_cast<const float4*>(blob + lp.w_off) + (size_t)h * lp.Np + n;
-                const float* a = in + i * kActStride + 4 * h;
-                const int ga = lp.Ka >> 3, ge = lp.Ke >> 3;
-                // Ka is a multiple of 32: batches of 4 groups, the next batch's 8 reads in flight under the 16 MFMAs of this one
-                float4 av[4], wv[4];
-                if (ga > 0) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { av[j] = *reinterpret_cast<const float4*>(a + 8 * j); wv[j] = w[j * wstep]; }
-                }
-                for (int g = 0; g < ga; g += 4) {
-                    float4 an[4], wn[4];
-                    const int gn = g + 4 < ga ? g + 4 : g;             // the last batch reads itself again: no branch around the reads
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { an[j] = *reinterpret_cast<const float4*>(a + 8 * (gn + j)); wn[j] = w[(gn + j) * wstep]; }
-                    __builtin_amdgcn_sched_barrier(0);                 // keep the reads above the MFMAs they overlap with
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc = mac8(acc, av[j], wv[j]);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { av[j] = an[j]; wv[j] = wn[j]; }
-                }
-                w += ga * wstep;
-                const float* e = emb + i * kEmbStride + lp.emb_off + 4 * h;
-                for (int g = 0; g < ge; ++g) acc = mac8(acc, *reinterpret_cast<const float4*>(e + 8 * g), w[g * wstep]);
-                // C/D map of the 32x32 forms: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const float v = activate(acc[r], lp.act, plan.beta);
-                    const long long p = p0 + row;
-                    if (lp.route == kGeoLast && t == n_col_tiles - 1) {
-                        if (i == 0 && p < N) {
-                            sdf[p] = -v;
-                            if (density != nullptr) {
-                                const float sgn = v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f);
-                                const float em = expm1f(-fabsf(v) / plan.b);
-                                density[p] = alpha * (0.5f + (0.5f * sgn) * em);
-                            }
-                        }
-                    } else if (lp.route == kColorLast) {
-                        if (i < 3 && p < N) color[(size_t)p * 3 + i] = v;
-                    } else {
-                        out[row * kActStride + n] = v;
-                    }
-                }
-            }
-            __syncthreads();
-            float* s = in; in = out; out = s;
-        }
-    }
-}
-
-// ---- the SDF with its gradient (include/ag_template_field_grad.h) ------------------------------------------------------------------------
+// ---- the SDF with its gradient (include/ag_template_field_grad.h): field_kernel<true> -----------------------------------------------------
 // Forward mode: a tile is kGradPoints = 8 points x 4 rows, MFMA row 4 q + c with q the point, c = 0 its value row and c = 1 .. 3 the
 // tangent d/dx_{c-1}.  A tangent row goes through the same linear maps as the value row (from 0 instead of the bias) and is multiplied
 // by the activation's derivative at the value row's pre-activation.  In the C/D map a lane holds rows (r & 3) + 8 (r >> 2) + 4 h: c = r & 3
 // and q = 2 (r >> 2) + h, so acc[4 j .. 4 j + 3] are the value and the three tangents of ONE point and the derivative needs no other lane.
-// The value rows see the instructions of template_field_kernel (a row of an MFMA does not depend on the other rows), so sdf and
+// The value rows see the instructions of field_kernel<false> (a row of an MFMA does not depend on the other rows), so sdf and
 // density are that kernel's bit for bit.  Same LDS, same blob, same plan as an SDF-only forward.
 constexpr int kGradPoints = kPoints / 4;
 
@@ -226,9 +138,12 @@ __device__ __forceinline__ void embed_tile_grad(float* emb, int L, const float* 
     for (int e = threadIdx.x; e < kPoints * pad; e += kThreads) emb[(e / pad) * kEmbStride + cols + e % pad] = 0.0f;
 }
 
-__global__ void __launch_bounds__(kThreads) template_field_grad_kernel(Plan plan, const float* __restrict__ blob, const float* __restrict__ xyz, long long N,
-                                                                       long long n_tiles, float* __restrict__ sdf, float* __restrict__ grad,
-                                                                       float* __restrict__ density)
+// kTangents false: the field (`vec3` = color, may be NULL); true: the SDF with its gradient (`vec3` = grad, `viewdirs` not read).  The tile
+// loop, the layer loop and the products are one text; the embedding, the accumulator's start and the epilogue are each kernel's own.
+template <bool kTangents>
+__global__ void __launch_bounds__(kThreads) field_kernel(Plan plan, const float* __restrict__ blob, const float* __restrict__ xyz,
+                                                         const float* __restrict__ viewdirs, long long N, long long n_tiles, float* __restrict__ sdf,
+                                                         float* __restrict__ density, float* __restrict__ vec3)
 {
     __shared__ __attribute__((aligned(16))) float act_lds[2 * kPoints * kActStride];
     __shared__ __attribute__((aligned(16))) float emb[kPoints * kEmbStride];
@@ -237,8 +152,13 @@ __global__ void __launch_bounds__(kThreads) template_field_grad_kernel(Plan plan
     const float alpha = 1.0f / plan.b;
 
     for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const long long p0 = tile * kGradPoints;
-        embed_tile_grad(emb, plan.L, xyz, p0, N);
+        const long long p0 = tile * (kTangents ? kGradPoints : kPoints);
+        if constexpr (kTangents) {
+            embed_tile_grad(emb, plan.L, xyz, p0, N);
+        } else {
+            embed_tile(emb, 0, plan.L, xyz, p0, N);
+            if (plan.Lv >= 0) embed_tile(emb, kEmbPos, plan.Lv, viewdirs, p0, N);   // some layer that runs concatenates the view embedding
+        }
         __syncthreads();
         float* in = act_lds + kPoints * kActStride;
         float* out = act_lds;
@@ -251,11 +171,12 @@ __global__ void __launch_bounds__(kThreads) template_field_grad_kernel(Plan plan
                 const float bias = blob[lp.b_off + n];
                 f32x16 acc;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = (r & 3) == 0 ? bias : 0.0f;
-                // the operand reads and the MFMA order of template_field_kernel
-                const float4* w = reinterpret_cast<const float4*>(blob + lp.w_off) + (size_t)h * lp.Np + n;
+                for (int r = 0; r < 16; ++r) acc[r] = (!kTangents || (r & 3) == 0) ? bias : 0.0f;
+                const float4* w = weights(blob, lp.w_off, lp.Np, n, h);
                 const float* a = in + i * kActStride + 4 * h;
-                const int ga = lp.Ka >> 3, ge = lp.Ke >> 3;
+                const int ga = lp.Ka >> 3;
+                // Ka is a multiple of 32: batches of 4 groups, the next batch's 8 reads in flight under the 16 MFMAs of this one.  This loop
+                // stands here and not behind a function of ag_mlp_tile.h: inlined from one, it is scheduled differently and both kernels lose time.
                 float4 av[4], wv[4];
                 if (ga > 0) {
 #pragma unroll
@@ -263,20 +184,36 @@ __global__ void __launch_bounds__(kThreads) template_field_grad_kernel(Plan plan
                 }
                 for (int g = 0; g < ga; g += 4) {
                     float4 an[4], wn[4];
-                    const int gn = g + 4 < ga ? g + 4 : g;
+                    const int gn = g + 4 < ga ? g + 4 : g;             // the last batch reads itself again: no branch around the reads
 #pragma unroll
                     for (int j = 0; j < 4; ++j) { an[j] = *reinterpret_cast<const float4*>(a + 8 * (gn + j)); wn[j] = w[(gn + j) * wstep]; }
-                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_sched_barrier(0);                 // keep the reads above the MFMAs they overlap with
 #pragma unroll
                     for (int j = 0; j < 4; ++j) acc = mac8(acc, av[j], wv[j]);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) { av[j] = an[j]; wv[j] = wn[j]; }
                 }
-                w += ga * wstep;
-                const float* e = emb + i * kEmbStride + lp.emb_off + 4 * h;
-                for (int g = 0; g < ge; ++g) acc = mac8(acc, *reinterpret_cast<const float4*>(e + 8 * g), w[g * wstep]);
+                acc = products(acc, emb + i * kEmbStride + lp.emb_off + 4 * h, w + ga * wstep, wstep, lp.Ke >> 3);
+                // the field's epilogue: 16 values of 16 points (no trip when kTangents)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
+                for (int r = 0; r < 16 && !kTangents; ++r) {
+                    const int row = cd_row(r, h);
+                    const float v = activate(acc[r], lp.act, plan.beta);
+                    const long long p = p0 + row;
+                    if (lp.route == kGeoLast && t == n_col_tiles - 1) {
+                        if (i == 0 && p < N) {
+                            sdf[p] = -v;
+                            if (density != nullptr) density[p] = sdf_density(v, plan.b, alpha);
+                        }
+                    } else if (lp.route == kColorLast) {
+                        if (i < 3 && p < N) vec3[(size_t)p * 3 + i] = v;
+                    } else {
+                        out[row * kActStride + n] = v;
+                    }
+                }
+                // the gradient's epilogue: value and three tangents of 4 points (no trip unless kTangents)
+#pragma unroll
+                for (int j = 0; j < 4 && kTangents; ++j) {
                     const float z = acc[4 * j];
                     const float v = activate(z, lp.act, plan.beta);
                     const float slope = activation_slope(z, lp.act, plan.beta);
@@ -285,14 +222,10 @@ __global__ void __launch_bounds__(kThreads) template_field_grad_kernel(Plan plan
                         const long long p = p0 + 2 * j + h;
                         if (i == 0 && p < N) {
                             sdf[p] = -v;
-                            grad[(size_t)p * 3 + 0] = t0;
-                            grad[(size_t)p * 3 + 1] = t1;
-                            grad[(size_t)p * 3 + 2] = t2;
-                            if (density != nullptr) {
-                                const float sgn = v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f);
-                                const float em = expm1f(-fabsf(v) / plan.b);
-                                density[p] = alpha * (0.5f + (0.5f * sgn) * em);
-                            }
+                            vec3[(size_t)p * 3 + 0] = t0;
+                            vec3[(size_t)p * 3 + 1] = t1;
+                            vec3[(size_t)p * 3 + 2] = t2;
+                            if (density != nullptr) density[p] = sdf_density(v, plan.b, alpha);
                         }
                     } else {
                         float* o = out + (8 * j + 4 * h) * kActStride + n;
@@ -308,9 +241,6 @@ __global__ void __launch_bounds__(kThreads) template_field_grad_kernel(Plan plan
         }
     }
 }
-
-inline int pad8(int v) { return (v + 7) / 8 * 8; }
-inline int pad32(int v) { return (v + 31) / 32 * 32; }
 
 // Validates `d` against the limits of the header and lays the blob out; returns the blob's floats through `total`.
 int make_plan(const AgTemplateFieldDesc* d, bool want_color, Plan& plan, size_t& total)
@@ -411,19 +341,16 @@ extern "C" int ag_template_field_forward(const AgTemplateFieldDesc* desc, const 
     const bool want_color = color != nullptr;
     if (int rc = make_plan(desc, want_color, plan, total)) return rc;
     if (want_color && desc->n_color == 0) { set_error("template field: colour requested from a field without a colour MLP"); return AG_ERR_INVALID_ARGUMENT; }
-    if (N < 0) { set_error("template field: N = %lld is negative", (long long)N); return AG_ERR_INVALID_ARGUMENT; }
-    if (blob_floats != total) { set_error("template field: blob of %zu floats, %zu expected for this table", blob_floats, total); return AG_ERR_INVALID_ARGUMENT; }
+    if (int rc = check_sizes("template field", N, INT64_MAX, blob_floats, total)) return rc;
     if (N == 0) return AG_OK;
-    if (!blob || !xyz || !sdf) { set_error("null pointer in ag_template_field_forward"); return AG_ERR_INVALID_ARGUMENT; }
-    if (reinterpret_cast<uintptr_t>(blob) % 16 != 0) { set_error("template field: the blob is not 16-byte aligned"); return AG_ERR_INVALID_ARGUMENT; }
-    int dev = 0, cus = 0;
-    if (int rc = check_hip(hipGetDevice(&dev), "template field hipGetDevice")) return rc;
-    if (int rc = check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "template field CU count")) return rc;
+    if (!xyz || !sdf) { set_error("null pointer in ag_template_field_forward"); return AG_ERR_INVALID_ARGUMENT; }
+    if (int rc = check_blob("template field", blob)) return rc;
     const long long n_tiles = (N + kPoints - 1) / kPoints;
-    const long long grid = n_tiles < 4ll * cus ? n_tiles : 4ll * cus;          // one workgroup fits a CU (LDS); the rest of a tile list is the grid-stride loop
-    hipLaunchKernelGGL(template_field_kernel, dim3((unsigned)grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), plan, blob, xyz, viewdirs,
+    unsigned grid = 0;                                                         // one workgroup fits a CU (LDS); the rest of a tile list is the grid-stride loop
+    if (int rc = persistent_grid(n_tiles, 4, "template field device query", &grid)) return rc;
+    hipLaunchKernelGGL(field_kernel<false>, dim3(grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), plan, blob, xyz, viewdirs,
                        (long long)N, n_tiles, sdf, density, color);
-    return check_hip(hipGetLastError(), "template_field_kernel");
+    return check_hip(hipGetLastError(), "field_kernel<false>");
 }
 
 extern "C" int ag_template_field_sdf_grad(const AgTemplateFieldDesc* desc, const float* blob, size_t blob_floats, const float* xyz, int64_t N, float* sdf,
@@ -438,17 +365,14 @@ extern "C" int ag_template_field_sdf_grad(const AgTemplateFieldDesc* desc, const
             return AG_ERR_INVALID_ARGUMENT;
         }
     }
-    if (N < 0) { set_error("template field: N = %lld is negative", (long long)N); return AG_ERR_INVALID_ARGUMENT; }
-    if (blob_floats != total) { set_error("template field: blob of %zu floats, %zu expected for this table", blob_floats, total); return AG_ERR_INVALID_ARGUMENT; }
+    if (int rc = check_sizes("template field gradient", N, INT64_MAX, blob_floats, total)) return rc;
     if (N == 0) return AG_OK;
-    if (!blob || !xyz || !sdf || !grad) { set_error("null pointer in ag_template_field_sdf_grad"); return AG_ERR_INVALID_ARGUMENT; }
-    if (reinterpret_cast<uintptr_t>(blob) % 16 != 0) { set_error("template field: the blob is not 16-byte aligned"); return AG_ERR_INVALID_ARGUMENT; }
-    int dev = 0, cus = 0;
-    if (int rc = check_hip(hipGetDevice(&dev), "template field hipGetDevice")) return rc;
-    if (int rc = check_hip(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "template field CU count")) return rc;
+    if (!xyz || !sdf || !grad) { set_error("null pointer in ag_template_field_sdf_grad"); return AG_ERR_INVALID_ARGUMENT; }
+    if (int rc = check_blob("template field gradient", blob)) return rc;
     const long long n_tiles = (N + kGradPoints - 1) / kGradPoints;
-    const long long grid = n_tiles < 4ll * cus ? n_tiles : 4ll * cus;          // as ag_template_field_forward
-    hipLaunchKernelGGL(template_field_grad_kernel, dim3((unsigned)grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), plan, blob, xyz, (long long)N,
-                       n_tiles, sdf, grad, density);
-    return check_hip(hipGetLastError(), "template_field_grad_kernel");
+    unsigned grid = 0;                                                         // as ag_template_field_forward
+    if (int rc = persistent_grid(n_tiles, 4, "template field gradient device query", &grid)) return rc;
+    hipLaunchKernelGGL(field_kernel<true>, dim3(grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), plan, blob, xyz,
+                       static_cast<const float*>(nullptr), (long long)N, n_tiles, sdf, density, grad);
+    return check_hip(hipGetLastError(), "field_kernel<true>");
 }

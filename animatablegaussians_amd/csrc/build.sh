@@ -19,7 +19,7 @@ FAST="-ffp-contract=fast"
 compile() { # src flags
   local src="$1"; shift
   local obj="$OBJ/$(basename "${src%.hip}").o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/ag_common.h" -nt "$obj" ] || [ "$HERE/../../include/ag_raster.h" -nt "$obj" ] || [ "$HERE/../../include/ag_avatar.h" -nt "$obj" ] || [ "$HERE/../../include/ag_styleunet.h" -nt "$obj" ] || [ "$HERE/../../include/ag_conv.h" -nt "$obj" ] || [ "$HERE/../../include/ag_lpips.h" -nt "$obj" ] || [ "$HERE/../../include/ag_smplx.h" -nt "$obj" ] || [ "$HERE/ag_sh.h" -nt "$obj" ] || [ "$HERE/../../include/ag_layers.h" -nt "$obj" ] || [ "$HERE/../../include/ag_optim.h" -nt "$obj" ] || [ "$HERE/../../include/ag_linear.h" -nt "$obj" ] || [ "$HERE/../../include/ag_subject_maps.h" -nt "$obj" ] || [ "$HERE/../../include/ag_metrics.h" -nt "$obj" ] || [ "$HERE/../../include/ag_weight_volume.h" -nt "$obj" ] || [ "$HERE/../../include/ag_targets.h" -nt "$obj" ] || [ "$HERE/../../include/ag_mesh_query.h" -nt "$obj" ] || [ "$HERE/../../include/ag_weight_diffuse.h" -nt "$obj" ] || [ "$HERE/../../include/ag_inverse_skinning.h" -nt "$obj" ] || [ "$HERE/../../include/ag_isosurface.h" -nt "$obj" ] || [ "$HERE/ag_isosurface_table.h" -nt "$obj" ] || [ "$HERE/../../include/ag_template_field.h" -nt "$obj" ] || [ "$HERE/../../include/ag_ray_march.h" -nt "$obj" ] || [ "$HERE/../../include/ag_template_field_grad.h" -nt "$obj" ] || [ "$HERE/../../include/ag_hand_fusion.h" -nt "$obj" ]; then
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ -n "$(find "$HERE" "$HERE/../../include" -maxdepth 1 -name '*.h' -newer "$obj" -print -quit)" ]; then
     echo "hipcc $(basename "$src") $*"
     rm -f "$obj"
     local log; log="$(mktemp)"

@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .template_field import _array, _pad, embed_dim
+from .mlp_blob import pack_rows, pad, ptr as _p, stream as _stream, unpack_rows
+from .template_field import _array, embed_dim
 
 MAX_LAYERS, MAX_MULTIRES = 8, 10             # include/ag_hand_fusion.h
 # How the closest-point kernel reads the face records (mesh_query.WALKS; time only, the results are bit-identical).  A hand has about
@@ -130,7 +131,7 @@ class HandField:
         out, off = [], 0
         for i, (w, _) in enumerate(self.layers):
             K = self.k_point if i == 0 else w.shape[1]
-            Kp, Np = _pad(K, 8), _pad(w.shape[0], 32)
+            Kp, Np = pad(K, 8), pad(w.shape[0], 32)
             out.append((K, Kp, Np, off, off + Kp * Np))
             off += Kp * Np + Np
         return out, off
@@ -139,9 +140,7 @@ class HandField:
         layout, total = self._layout()
         blob = np.zeros(total, np.float32)
         for i, ((w, b), (K, Kp, Np, w_off, b_off)) in enumerate(zip(self.layers, layout)):
-            rows = np.zeros((Kp, Np), np.float32)                           # [packed k][packed n]
-            rows[:K, :w.shape[0]] = w[:, :K].T
-            blob[w_off:b_off] = rows.reshape(Kp // 4, 4, Np).transpose(0, 2, 1).reshape(-1)
+            blob[w_off:b_off] = pack_rows(w[:, :K].T, Kp, Np)
             blob[b_off:b_off + w.shape[0]] = self.folded_bias(hand_pose) if i == 0 else b
         return blob
 
@@ -154,7 +153,7 @@ class HandField:
             raise ValueError(f"blob of {blob.shape}, expected ({total},)")
         layers, padding = [], []
         for (w, _), (K, Kp, Np, w_off, b_off) in zip(self.layers, layout):
-            rows = blob[w_off:b_off].reshape(Kp // 4, Np, 4).transpose(0, 2, 1).reshape(Kp, Np)
+            rows = unpack_rows(blob[w_off:b_off], Kp, Np)
             bias = blob[b_off:b_off + Np]
             layers.append((np.ascontiguousarray(rows[:K, :w.shape[0]].T), bias[:w.shape[0]].copy()))
             padding += [rows[K:].reshape(-1), rows[:K, w.shape[0]:].reshape(-1), bias[w.shape[0]:]]
@@ -263,14 +262,6 @@ class PreparedHands:
         if not isinstance(hands, dict) or not set(SIDES) <= set(hands):
             raise ValueError("hands must be dict(left=dict(v=, n=, f=, cano_v=), right=dict(...))")
         self.left, self.right = _Hand("left", hands["left"], dev), _Hand("right", hands["right"], dev)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(None)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def active_mask(cano_xyz: torch.Tensor, left_box, right_box, centre_y: float) -> torch.Tensor:

@@ -25,15 +25,12 @@ import torch
 
 from . import _lib
 from . import isosurface
+from .mlp_blob import pack_rows, pad, ptr, stream, unpack_rows
 
 ACT_NONE, ACT_SOFTPLUS, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3          # include/ag_template_field.h
 CONCAT_NONE, CONCAT_POSITION, CONCAT_VIEW = 0, 1, 2
 MAX_LAYERS, MAX_WIDTH, MAX_MULTIRES, MAX_MULTIRES_VIEW = 8, 512, 10, 4
 GRID_CHUNK = 256 * 256 * 4          # points per launch of sdf_grid, the chunk of the reference's test_geometry
-
-
-def _pad(v: int, m: int) -> int:
-    return (v + m - 1) // m * m
 
 
 def embed_dim(multires: int) -> int:
@@ -235,7 +232,7 @@ class TemplateField:
         out, off = [], 0
         for net, K, width, act, concat, prev in self.layers:
             e_cols = K - prev
-            Ke, Np = _pad(e_cols, 8), _pad(width, 32)
+            Ke, Np = pad(e_cols, 8), pad(width, 32)
             out.append((prev, e_cols, Ke, Np, off, off + (prev + Ke) * Np))
             off += (prev + Ke) * Np + Np
         return out, off
@@ -244,7 +241,7 @@ class TemplateField:
         """Packed column of every output column of layer ``i`` (the last geometry layer: features first, the SDF column last)."""
         net, K, width, *_ = self.layers[i]
         if net == "geo" and i == len(self.geo) - 1:
-            return np.concatenate([[_pad(width, 32) - 32], np.arange(width - 1)]).astype(np.int64)
+            return np.concatenate([[pad(width, 32) - 32], np.arange(width - 1)]).astype(np.int64)
         return np.arange(width, dtype=np.int64)
 
     def pack(self) -> np.ndarray:
@@ -254,7 +251,7 @@ class TemplateField:
             rows = np.zeros((Ka + Ke, Np), np.float32)                      # [packed k][packed n]
             cols = self._columns(i)
             rows[:Ka + e_cols, cols] = w.T
-            blob[w_off:b_off] = rows.reshape((Ka + Ke) // 4, 4, Np).transpose(0, 2, 1).reshape(-1)
+            blob[w_off:b_off] = pack_rows(rows, Ka + Ke, Np)
             blob[b_off + cols] = b
         return blob
 
@@ -266,7 +263,7 @@ class TemplateField:
             raise ValueError(f"blob of {blob.shape}, expected ({total},)")
         layers, padding = [], []
         for i, (Ka, e_cols, Ke, Np, w_off, b_off) in enumerate(layout):
-            rows = blob[w_off:b_off].reshape((Ka + Ke) // 4, Np, 4).transpose(0, 2, 1).reshape(Ka + Ke, Np)
+            rows = unpack_rows(blob[w_off:b_off], Ka + Ke, Np)
             bias = blob[b_off:b_off + Np]
             cols = self._columns(i)
             layers.append((np.ascontiguousarray(rows[:Ka + e_cols, cols].T), bias[cols].copy()))
@@ -287,11 +284,9 @@ class TemplateField:
         dev = xyz.device
         blob = self._blob_on(dev)
         d = self.desc()
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
         with _lib.on_device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(L.ag_template_field_forward(ctypes.byref(d), ctypes.c_void_p(blob.data_ptr()), blob.numel(), p(xyz), p(viewdirs), xyz.shape[0],
-                                                   p(sdf), p(density), p(color), stream), "ag_template_field_forward")
+            _lib.check(L.ag_template_field_forward(ctypes.byref(d), ptr(blob), blob.numel(), ptr(xyz), ptr(viewdirs), xyz.shape[0], ptr(sdf), ptr(density),
+                                                   ptr(color), stream(dev)), "ag_template_field_forward")
 
     def __call__(self, xyz: torch.Tensor, viewdirs: Optional[torch.Tensor] = None, want=("sdf",)):
         """``xyz`` [N, 3] float32 on the GPU -> dict of device tensors: ``sdf`` [N, 1] (always; positive inside, ``template.py:123``),
@@ -337,11 +332,9 @@ class TemplateField:
         if n:
             blob = self._blob_on(dev)
             d = self.desc()
-            p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
             with _lib.on_device(dev):
-                stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                _lib.check(_lib.lib().ag_template_field_sdf_grad(ctypes.byref(d), p(blob), blob.numel(), p(xyz), n, p(out["sdf"]), p(out["normal"]),
-                                                                 p(out.get("density")), stream), "ag_template_field_sdf_grad")
+                _lib.check(_lib.lib().ag_template_field_sdf_grad(ctypes.byref(d), ptr(blob), blob.numel(), ptr(xyz), n, ptr(out["sdf"]), ptr(out["normal"]),
+                                                                 ptr(out.get("density")), stream(dev)), "ag_template_field_sdf_grad")
         out["cano_xyz"] = xyz
         return out
 

@@ -20,24 +20,16 @@ and no PyTorch fallback.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import torch
 
 from . import _lib
+from .mlp_blob import ptr as _ptr, stream as _stream
 
 MIN_SAMPLES, MAX_SAMPLES = 2, 1024          # include/ag_ray_march.h
 OUTPUTS = ("rgb_map", "acc_map", "depth_map", "disp_map", "weights")
 SAMPLINGS = ("smpl", "uniform", "depth")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(None)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _f32(t, name: str, shape, dev=None) -> torch.Tensor:
