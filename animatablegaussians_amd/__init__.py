@@ -1,15 +1,18 @@
 """MI355X-native Animatable Gaussians.  The modules are imported by name (``from animatablegaussians_amd import losses``); the two
 loader-facing functions of ``targets``, the template stage's ``TemplateField`` with ``eikonal_loss`` and its renderer (``render``,
-``render_normals``, ``near_far_smpl``, ``sample_pts_on_rays``, ``composite`` of ``template_render``) and the hand fusion (``HandField``,
+``render_normals``, ``near_far_smpl``, ``sample_pts_on_rays``, ``composite`` and, for training, ``composite_backward``, ``laplace_density``,
+``render_train``, ``training_loss`` of ``template_render``) and the hand fusion (``HandField``,
 ``hand_meshes``, ``fuse_hands``, ``hand_fields_from_checkpoint`` of ``hand_fusion``) are also reachable from the package,
 resolved on first use so that importing the package stays free of side effects."""
 
 __all__ = ["prepare_targets", "boundary_mask", "TemplateField", "eikonal_loss", "render", "render_normals", "near_far_smpl",
-           "sample_pts_on_rays", "composite", "HandField", "hand_meshes", "fuse_hands", "hand_fields_from_checkpoint"]
+           "sample_pts_on_rays", "composite", "composite_backward", "laplace_density", "render_train", "training_loss", "HandField", "hand_meshes", "fuse_hands", "hand_fields_from_checkpoint"]
 
 _HOME = {"prepare_targets": "targets", "boundary_mask": "targets", "TemplateField": "template_field", "eikonal_loss": "template_field",
          "render": "template_render", "render_normals": "template_render",
          "near_far_smpl": "template_render", "sample_pts_on_rays": "template_render", "composite": "template_render",
+         "composite_backward": "template_render", "laplace_density": "template_render", "render_train": "template_render",
+         "training_loss": "template_render",
          "HandField": "hand_fusion", "hand_meshes": "hand_fusion", "fuse_hands": "hand_fusion", "hand_fields_from_checkpoint": "hand_fusion"}
 
 

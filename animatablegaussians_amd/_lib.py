@@ -325,6 +325,11 @@ SYMBOLS = [
     ("ag_ray_near_far", ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, ctypes.c_int64, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("ag_ray_sample", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("ag_ray_composite", ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # include/ag_ray_march_grad.h
+    ("ag_ray_composite_backward", ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("ag_laplace_density", ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, c_vp, c_vp]),
+    ("ag_laplace_density_backward_workspace_bytes", c_sz, [ctypes.c_int64]),
+    ("ag_laplace_density_backward", ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_targets.h
     ("ag_prepare_targets", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_styleunet.h

@@ -12,10 +12,14 @@
 #include <math.h>
 
 #include "ag_common.h"
+#include "ag_ray_scan.h"
 #include "../../include/ag_ray_march.h"
 
 namespace ag {
 namespace {
+
+using ray::bad_counts;
+using ray::butterfly_sum;
 
 constexpr int kThreads = 256;
 constexpr int kVertexTile = 1024;                  // vertices per LDS tile: 12 KiB
@@ -131,15 +135,8 @@ __global__ void __launch_bounds__(kThreads) ray_sample_kernel(const float* __res
 }
 
 // ---- compositing ----------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float butterfly_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One wavefront per ray, four rays per workgroup; lane l of chunk k is sample 64 k + l.  The order of the product scan and of the
-// sums is the header's.  The loop count is uniform over the wavefront, so every lane takes part in every cross-lane move.
+// sums is the header's, stated once in ag_ray_scan.h for this kernel and the backward.  The loop count is uniform over the wavefront, so every lane takes part in every cross-lane move.
 __global__ void __launch_bounds__(kThreads) ray_composite_kernel(const float* __restrict__ density, const float* __restrict__ color,
                                                                  const float* __restrict__ z_vals, long long R, int S, int white_bkgd,
                                                                  float* __restrict__ rgb_map, float* __restrict__ acc_map, float* __restrict__ depth_map,
@@ -155,23 +152,14 @@ __global__ void __launch_bounds__(kThreads) ray_composite_kernel(const float* __
         const bool valid = s < S;
         float alpha = 0.f, f = 1.f, z = 0.f;
         if (valid) {
-            z = z_vals[row + s];
-            const float zn = z_vals[row + min(s + 1, S - 1)];
-            const float zl = s == S - 1 ? z_vals[row + S - 2] : z;
-            const float dist = zn - zl;
+            const float dist = ray::sample_dist(z_vals, row, s, S, z);
             alpha = 1.f - expf(-density[row + s] * dist);
             f = (1.f - alpha) + 1e-10f;
         }
-        float p = f;
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const float q = __shfl_up(p, o, 64);
-            if (lane >= o) p = q * p;
-        }
-        const float before = __shfl_up(p, 1, 64);
-        const float T = carry * (lane == 0 ? 1.f : before);
+        const float p = ray::product_scan(f, lane);
+        const float T = ray::transmittance(p, carry, lane);
         const float w = alpha * T;                  // 0 past S - 1
-        carry = carry * __shfl(p, 63, 64);
+        carry = ray::next_carry(p, carry);
         if (valid && weights) weights[row + s] = w;
         float c0 = 0.f, c1 = 0.f, c2 = 0.f;
         if (valid && color) { c0 = color[3 * (row + s)]; c1 = color[3 * (row + s) + 1]; c2 = color[3 * (row + s) + 2]; }
@@ -194,17 +182,6 @@ __global__ void __launch_bounds__(kThreads) ray_composite_kernel(const float* __
             disp_map[ray] = 1.f / (q <= 1e-10f ? 1e-10f : q);     // NaN stays NaN (torch.max)
         }
     }
-}
-
-bool bad_counts(const char* what, long long R, int S)
-{
-    if (R < 0) { set_error("%s: R = %lld is negative", what, R); return true; }
-    if (S < AG_RAY_MIN_SAMPLES || S > AG_RAY_MAX_SAMPLES) {
-        set_error("%s: S = %d is outside %d .. %d", what, S, AG_RAY_MIN_SAMPLES, AG_RAY_MAX_SAMPLES);
-        return true;
-    }
-    if (R > (1ll << 31) / S || R > (1ll << 25)) { set_error("%s: R = %lld rays of %d samples exceed one launch (2^25 rays, 2^31 samples)", what, R, S); return true; }
-    return false;
 }
 
 }  // namespace

@@ -66,6 +66,8 @@ compile "$HERE/ag_isosurface.hip" $EXACT &
 compile "$HERE/ag_template_field.hip" $EXACT &
 # near / far, the sample positions and the compositing sums are stated op by op in include/ag_ray_march.h
 compile "$HERE/ag_ray_march.hip" $EXACT &
+# the reverse recurrence of the compositing and the density's derivatives are stated op by op in include/ag_ray_march_grad.h
+compile "$HERE/ag_ray_march_grad.hip" $EXACT &
 # the gates, the interpolation, the hand's signed distance, the blend and the density are stated op by op in include/ag_hand_fusion.h
 compile "$HERE/ag_hand_fusion.hip" $EXACT &
 fail=0

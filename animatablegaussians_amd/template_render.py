@@ -12,8 +12,15 @@ posed space (``inverse_skinning``), the fused field (``template_field.TemplateFi
 ``render(..., hands=)`` fuses the hand fields into the body field at every sample (``template.py:365-366``, ``hand_fusion.fuse_hands``) between
 the field and the compositing: what a checkpoint trained with ``with_hand: true`` needs.
 
-NOT here: any backward, the training-mode noise on the view directions, the
-scattering through ``mask_within_patch`` and the dataset-side ray selection of ``nerf_util`` (``get_rays``, ``get_near_far``, patch
+Training (``include/ag_ray_march_grad.h``): ``composite`` is differentiable in ``density`` and ``color`` (``composite_backward``: one
+reverse scan per ray, no division by ``1 - alpha + 1e-10``), ``laplace_density`` is ``LaplaceDensity`` with a learned ``beta``,
+differentiable in both arguments, ``render_train`` is ``TemplateNet.render`` in training mode (the caller's noise on the view
+directions, the scattering through ``mask_within_patch``) around any differentiable field callable, and ``training_loss`` the colour
+and mask L1 terms of ``main_template.py:37-51``.
+
+NOT here: the reverse pass of the fused MLP (``render_train`` takes a torch callable as the field until it exists), the eikonal
+term's second-order pass, the hand fusion's backward, gradients to ``z_vals``, and the dataset-side ray selection of ``nerf_util``
+(``get_rays``, ``get_near_far``, patch
 sampling): the caller brings the rays and the box near / far, as the reference's batch does.  Near / far is pinned to the header's
 formulas: the reference's kernel is CUDA and was never run beside this one.  Every tensor must be on the GPU; there is no host path
 and no PyTorch fallback.
@@ -154,24 +161,154 @@ def _outputs(want, R, S, dev):
 def composite(density: torch.Tensor, color: Optional[torch.Tensor], z_vals: torch.Tensor, white_bkgd: bool = False, want=("rgb_map", "acc_map")):
     """``template.py:345-346, 372-374`` + ``nerf_util.raw2outputs``: ``density`` [R, S] (or [R * S, 1], the field's shape), ``color``
     [R, S, 3] (or [R * S, 3]; None for a field without colour), ``z_vals`` [R, S] -> dict with ``rgb_map`` [R, 3], ``acc_map`` [R] and, when
-    named in ``want``, ``depth_map`` [R], ``disp_map`` [R], ``weights`` [R, S].  alpha is formed inside the kernel."""
+    named in ``want``, ``depth_map`` [R], ``disp_map`` [R], ``weights`` [R, S].  alpha is formed inside the kernel.
+
+    Differentiable in ``density`` and ``color``: when grad mode is on and either requires grad, the same launch is recorded for autograd
+    and its backward is ``composite_backward``; ``disp_map`` is not differentiable, and a ``z_vals`` that requires grad is refused.  In
+    every other case nothing but the forward launch runs; the maps' bits are the same either way."""
     want = _want(want)
+    grad_mode = torch.is_grad_enabled()
+    if grad_mode and isinstance(z_vals, torch.Tensor) and z_vals.requires_grad:
+        raise ValueError("z_vals requires grad: there is no gradient to the sample positions (they carry no parameters in the reference); detach z_vals")
+    tracked = grad_mode and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (density, color))
+    density_in, color_in, z = _composite_inputs(density, color, z_vals)
+    R, S = z.shape
+    if color_in is None and "rgb_map" in want:
+        raise ValueError("rgb_map needs color")
+    if "rgb_map" not in want:
+        color_in = None
+    if tracked:
+        # the same launch and the same bits, recorded for autograd (composite_backward)
+        maps = _Composite.apply(density_in, color_in, z, bool(white_bkgd), want)
+        return {k: v for k, v in zip([k for k in OUTPUTS if k in want or k == "acc_map"], maps) if k in want}
+    out = _outputs(want, R, S, z.device)
+    _composite_into(density_in.detach().contiguous(), None if color_in is None else color_in.detach().contiguous(), z, white_bkgd, out)
+    return {k: v for k, v in out.items() if k in want}
+
+
+def _composite_inputs(density, color, z_vals):
+    """The checks of ``composite`` -> ``density`` [R, S] and ``color`` [R, S, 3] (or None) still attached to their graphs, ``z`` detached."""
     z = _f32(z_vals, "z_vals", (None, None))
     R, S = z.shape
     _samples(S)
     if not isinstance(density, torch.Tensor) or density.numel() != R * S:
         raise ValueError(f"density must hold {R} x {S} values, got {tuple(density.shape) if isinstance(density, torch.Tensor) else type(density)}")
-    density = _f32(density.reshape(R, S), "density", (R, S), z.device)
-    if color is None:
-        if "rgb_map" in want:
-            raise ValueError("rgb_map needs color")
-    else:
+    density = density.reshape(R, S)
+    _f32(density, "density", (R, S), z.device)
+    if color is not None:
         if not isinstance(color, torch.Tensor) or color.numel() != R * S * 3 or color.shape[-1] != 3:
             raise ValueError(f"color must hold {R} x {S} x 3 values, got {tuple(color.shape) if isinstance(color, torch.Tensor) else type(color)}")
-        color = _f32(color.reshape(R, S, 3), "color", (R, S, 3), z.device) if "rgb_map" in want else None
-    out = _outputs(want, R, S, z.device)
-    _composite_into(density, color, z, white_bkgd, out)
-    return {k: v for k, v in out.items() if k in want}
+        color = color.reshape(R, S, 3)
+        _f32(color, "color", (R, S, 3), z.device)
+    return density, color, z
+
+
+GRADS = ("rgb_map", "acc_map", "depth_map", "weights")
+
+
+def _composite_backward(density, color, z, white_bkgd, g, need_density, need_color):
+    """One ``ag_ray_composite_backward`` launch on detached contiguous inputs; ``g``: name -> contiguous float32 gradient."""
+    R, S = z.shape
+    gd = torch.empty((R, S), dtype=torch.float32, device=z.device) if need_density else None
+    gc = torch.empty((R, S, 3), dtype=torch.float32, device=z.device) if need_color else None
+    if R:
+        with _lib.on_device(z.device):
+            _lib.check(_lib.lib().ag_ray_composite_backward(_ptr(density), _ptr(color), _ptr(z), R, S, 1 if white_bkgd else 0, _ptr(g.get("rgb_map")),
+                                                            _ptr(g.get("acc_map")), _ptr(g.get("depth_map")), _ptr(g.get("weights")), _ptr(gd), _ptr(gc),
+                                                            _stream(z.device)), "ag_ray_composite_backward")
+    return gd, gc
+
+
+def composite_backward(density: torch.Tensor, color: Optional[torch.Tensor], z_vals: torch.Tensor, grads: dict, white_bkgd: bool = False):
+    """The gradient of ``composite`` (``include/ag_ray_march_grad.h``): ``grads`` holds the upstream gradients of any of ``rgb_map`` [R, 3],
+    ``acc_map`` [R], ``depth_map`` [R], ``weights`` [R, S] (a missing one is zero; none at all gives zeros) -> ``{"density": [R, S],
+    "color": [R, S, 3]}``.  ``color`` is None in the result when ``grads`` has no ``rgb_map`` (the colour then receives no gradient) or
+    no ``color`` was given.  There is no gradient to ``z_vals`` and none through ``disp_map``."""
+    if not isinstance(grads, dict) or not set(grads) <= set(GRADS):
+        raise ValueError(f"grads names {', '.join(repr(k) for k in GRADS)}, got {sorted(grads) if isinstance(grads, dict) else type(grads)}")
+    density, color, z = _composite_inputs(density, color, z_vals)
+    R, S = z.shape
+    shapes = {"rgb_map": (R, 3), "acc_map": (R,), "depth_map": (R,), "weights": (R, S)}
+    g = {k: _f32(v, f"grads[{k!r}]", shapes[k], z.device) for k, v in grads.items() if v is not None}
+    if "rgb_map" in g and color is None:
+        raise ValueError("grads['rgb_map'] needs color")
+    color = color.detach().contiguous() if "rgb_map" in g else None
+    gd, gc = _composite_backward(density.detach().contiguous(), color, z, white_bkgd, g, True, color is not None)
+    return {"density": gd, "color": gc}
+
+
+class _Composite(torch.autograd.Function):
+    """``composite`` for autograd: the forward is ``_composite_into``, the backward ``ag_ray_composite_backward``."""
+
+    @staticmethod
+    def forward(ctx, density, color, z, white_bkgd, want):
+        density = density.detach().contiguous()
+        color = None if color is None else color.detach().contiguous()
+        R, S = z.shape
+        out = _outputs(want, R, S, z.device)
+        _composite_into(density, color, z, white_bkgd, out)
+        ctx.save_for_backward(density, color, z)
+        ctx.white_bkgd, ctx.names = white_bkgd, tuple(out)
+        ctx.set_materialize_grads(False)
+        if "disp_map" in out:
+            ctx.mark_non_differentiable(out["disp_map"])
+        return tuple(out.values())
+
+    @staticmethod
+    def backward(ctx, *upstream):
+        density, color, z = ctx.saved_tensors
+        g = {k: v.contiguous() for k, v in zip(ctx.names, upstream) if v is not None and k in GRADS}
+        need_density, need_color = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and "rgb_map" in g
+        if not need_density and not need_color:
+            return None, None, None, None, None
+        gd, gc = _composite_backward(density, color if "rgb_map" in g else None, z, ctx.white_bkgd, g, need_density, need_color)
+        return gd, gc, None, None, None
+
+
+class _LaplaceDensity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sdf, beta):
+        s = sdf.detach().contiguous()
+        b = beta.detach().contiguous()
+        out = torch.empty_like(s)
+        if s.numel():
+            with _lib.on_device(s.device):
+                _lib.check(_lib.lib().ag_laplace_density(_ptr(s), s.numel(), _ptr(b), _ptr(out), _stream(s.device)), "ag_laplace_density")
+        ctx.save_for_backward(s, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        s, b = ctx.saved_tensors
+        need_sdf, need_beta = ctx.needs_input_grad
+        if not need_sdf and not need_beta:
+            return None, None
+        g = g.contiguous()
+        N, L = s.numel(), _lib.lib()
+        gs = torch.empty_like(s) if need_sdf else None
+        gb = torch.empty_like(b) if need_beta else None
+        ws = torch.empty(int(L.ag_laplace_density_backward_workspace_bytes(N)) // 8, dtype=torch.float64, device=s.device) if need_beta else None
+        if N or need_beta:
+            with _lib.on_device(s.device):
+                _lib.check(L.ag_laplace_density_backward(_ptr(s), _ptr(g), N, _ptr(b), _ptr(gs), _ptr(gb), _ptr(ws), _stream(s.device)),
+                           "ag_laplace_density_backward")
+        return gs, gb
+
+
+def laplace_density(sdf: torch.Tensor, beta) -> torch.Tensor:
+    """``LaplaceDensity`` (``network/density.py:22-36``) of the field's ``sdf`` (positive inside; any shape) -> the density, same shape:
+    ``(1 / b) * (0.5 + 0.5 * sign(-sdf) * expm1(-|sdf| / b))`` with ``b = |beta| + 1e-4`` formed on the device from ``beta``, a one-element
+    float32 device tensor (the learned parameter: no host read) or a float.  For the same ``sdf`` it equals ``TemplateField``'s density
+    bit for bit.  Differentiable in ``sdf`` and in a tensor ``beta`` (``ag_laplace_density_backward``; the gradient of ``beta`` is
+    bit-identical between calls)."""
+    if not isinstance(sdf, torch.Tensor) or not sdf.is_cuda or sdf.dtype != torch.float32:
+        raise ValueError("sdf must be a float32 tensor on the GPU (there is no host path)")
+    if isinstance(beta, torch.Tensor):
+        if beta.device != sdf.device or beta.dtype != torch.float32 or beta.numel() != 1:
+            raise ValueError(f"beta must be a one-element float32 tensor on {sdf.device} or a float")
+    else:
+        beta = torch.tensor([float(beta)], dtype=torch.float32, device=sdf.device)
+    return _LaplaceDensity.apply(sdf, beta)
 
 
 def _march_setup(ray_o, ray_d, near, far, space, sampling, live_smpl_v, radius, dist, near_sur_dist, n_samples, u, chunk_size, live):
@@ -330,3 +467,91 @@ def render_normals(field, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.
         out["normal"] = normal
     out = {k: v for k, v in out.items() if k in want}
     return {k: v[None] for k, v in out.items()} if batched else out
+
+
+def render_train(field_fn, beta, ray_o: torch.Tensor, ray_d: torch.Tensor, near: torch.Tensor, far: torch.Tensor, *, space: str = "cano",
+                 sampling: str = "smpl", live_smpl_v: Optional[torch.Tensor] = None, radius: float = 0.1, dist: Optional[torch.Tensor] = None,
+                 near_sur_dist: Optional[float] = None, n_samples: int = 64, u: Optional[torch.Tensor] = None, chunk_size: Optional[int] = None,
+                 dir_noise: Optional[torch.Tensor] = None, mask_within_patch: Optional[torch.Tensor] = None, white_bkgd: bool = False,
+                 live: Optional[dict] = None, want=("rgb_map", "acc_map"), hands: Optional[dict] = None):
+    """``TemplateNet.render`` in training mode for one batch element, differentiable with respect to whatever ``field_fn`` and ``beta``
+    hold: ``render``'s rays, samplings, spaces and checks, then per chunk
+
+    ``field_fn(cano_pts [N, 3], viewdirs [N, 3]) -> (sdf [N, 1] or [N], color [N, 3])``, any differentiable callable (a torch module until
+    the fused field has a reverse pass), ``laplace_density(sdf, beta)`` and ``composite``.
+
+    ``u`` [R, S] perturbs the samples (``perturb = self.training``) and ``dir_noise`` [R * S, 3] (the reference's ``randn * 0.1``) is added
+    to the unit view directions, which are normalised again (``template.py:358-362``); both are the caller's random numbers, and
+    without them nothing is perturbed.  ``chunk_size`` None takes all rays in one chunk, as the reference does in training.  Posed
+    space maps the samples without a graph (the reference's ``transform_live2cano`` is under ``no_grad`` for the points it returns).
+    ``mask_within_patch`` [P] (bool, R of them set): ``rgb_map`` / ``acc_map`` are scattered into zeros of length P
+    (``template.py:394-403``); the other maps stay per ray.
+
+    -> dict of the maps of ``want`` plus ``cano_pts`` [R * S, 3] (detached: a caller forms its own eikonal term there), ``z_vals`` [R, S]
+    and ``mask_within_patch`` as given.  ``hands=`` is refused: the hand fusion has no backward."""
+    if hands is not None:
+        raise ValueError("hands: the hand fusion's backward is not built; render_train renders the body field alone")
+    if not callable(field_fn):
+        raise ValueError("field_fn must be callable: (cano_pts [N, 3], viewdirs [N, 3]) -> (sdf [N, 1], color [N, 3])")
+    want = _want(want)
+    n_rays = ray_o.shape[-2] if isinstance(ray_o, torch.Tensor) and ray_o.dim() >= 2 else 1
+    setup = _march_setup(ray_o, ray_d, near, far, space, sampling, live_smpl_v, radius, dist, near_sur_dist, n_samples, u,
+                         max(1, n_rays) if chunk_size is None else chunk_size, live)
+    o, t, batched = setup[0], setup[4], setup[8]
+    R, S, dev = o.shape[0], t.shape[0], o.device
+    if dir_noise is not None:
+        dir_noise = _f32(dir_noise[0] if batched and dir_noise.dim() == 3 else dir_noise, "dir_noise", (R * S, 3), dev)
+    if mask_within_patch is not None:
+        m = mask_within_patch
+        if not isinstance(m, torch.Tensor) or m.device != dev or m.dtype != torch.bool or m.dim() not in (1, 2) or (m.dim() == 2 and m.shape[0] != 1):
+            raise ValueError(f"mask_within_patch must be a bool tensor [P] (or [1, P]) on {dev}")
+        m = m.reshape(-1)
+        if int(m.sum()) != R:
+            raise ValueError(f"mask_within_patch marks {int(m.sum())} rays, the batch has {R}")
+    parts, pts_all, z_all = [], [], []
+    for r0, r1, pts, z, dirs, _ in _chunks(setup, space, live, True):
+        dirs = dirs.view(-1, 3)
+        if dir_noise is not None:
+            dirs = dirs + dir_noise[r0 * S:r1 * S]
+            dirs = dirs / torch.norm(dirs, dim=-1, keepdim=True)
+        pts = pts.detach()
+        sdf, color = field_fn(pts, dirs)
+        parts.append(composite(laplace_density(sdf, beta), color, z, white_bkgd, want))
+        pts_all.append(pts)
+        z_all.append(z)
+    if not parts:                                   # R = 0
+        parts, pts_all, z_all = [_outputs(want, 0, S, dev)], [torch.empty((0, 3), device=dev)], [torch.empty((0, S), device=dev)]
+    out = {k: torch.cat([p[k] for p in parts]) if len(parts) > 1 else parts[0][k] for k in want}
+    if mask_within_patch is not None:
+        for k in ("rgb_map", "acc_map"):
+            if k in out:
+                full = torch.zeros((m.shape[0],) + tuple(out[k].shape[1:]), dtype=torch.float32, device=dev)
+                out[k] = full.index_put((m,), out[k])
+    out["cano_pts"] = torch.cat(pts_all) if len(pts_all) > 1 else pts_all[0]
+    out["z_vals"] = torch.cat(z_all) if len(z_all) > 1 else z_all[0]
+    if batched:
+        out = {k: v[None] for k, v in out.items()}
+    out["mask_within_patch"] = mask_within_patch
+    return out
+
+
+def training_loss(out: dict, color_gt: torch.Tensor, mask_gt: torch.Tensor, weights: dict):
+    """The colour and mask terms of ``main_template.py:37-51`` on ``render_train``'s output: ``total = weights["color"] * L1(rgb_map,
+    color_gt) + weights["mask"] * L1(acc_map, mask_gt)``, means over every element -> ``(total, {"color_loss": .., "mask_loss": ..})``
+    (tensors: no host read).  With ``out["mask_within_patch"]`` the targets outside the patch count as 0 (``template.py:400-401``), without
+    being modified.  A term whose map is missing from ``out`` is left out, as in the reference.  Plain torch."""
+    total, terms = None, {}
+    m = out.get("mask_within_patch")
+    for name, key, gt, w in (("color_loss", "rgb_map", color_gt, "color"), ("mask_loss", "acc_map", mask_gt, "mask")):
+        if key not in out:
+            continue
+        pred = out[key]
+        gt = gt.reshape(pred.shape)
+        if m is not None:
+            keep = m.reshape(pred.shape[:-1] if key == "rgb_map" else pred.shape)
+            gt = torch.where(keep[..., None] if key == "rgb_map" else keep, gt, torch.zeros_like(gt))
+        terms[name] = torch.nn.functional.l1_loss(pred, gt)
+        total = float(weights[w]) * terms[name] if total is None else total + float(weights[w]) * terms[name]
+    if total is None:
+        raise ValueError("out holds neither rgb_map nor acc_map")
+    return total, terms
