@@ -451,6 +451,19 @@ def on_device(dev):
     return torch.cuda.device(dev)
 
 
+def stream(dev) -> ctypes.c_void_p:
+    """The current HIP stream of ``dev`` as the ``void*`` every native call takes last."""
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def scratch(nfloats: int, ws_bytes: int, dev):
+    """One buffer for a layer call's intermediates (``nfloats`` floats) and its convolution workspace (include/ag_layers.h), both
+    256-byte aligned.  Returns (tensor that owns the memory, scratch address, workspace address)."""
+    buf = torch.empty(nfloats * 4 + ws_bytes + 512, dtype=torch.uint8, device=dev)
+    base = (buf.data_ptr() + 255) & ~255
+    return buf, base, base + ((nfloats * 4 + 255) & ~255)
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().ag_last_error().decode("utf-8", "replace")

@@ -12,14 +12,11 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import stream as _stream
 
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _chk(t: torch.Tensor, name: str) -> torch.Tensor:

@@ -13,6 +13,7 @@ import os
 import torch
 
 from . import _lib
+from ._lib import stream as _stream
 
 AG_CONV, AG_CONV_TRANSPOSE = 0, 1
 MATH_MODES = {"fp32": 0, "split_bf16": 1, "split_bf16x3": 2, "split_f16": 3, "f16": 4}      # include/ag_conv.h AgConvMath
@@ -56,10 +57,6 @@ if os.environ.get("AG_CONV_MATH"):          # A/B hook for the profiles/ scripts
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _desc(kind, Cin, Cout, H, W, k, stride, padding, weight_scale=1.0):

@@ -45,9 +45,6 @@ inline bool table_complete(const PtrTable& t, int G)
 // y [G][C][HW] = lrelu(x + nw_g[0] * noise_g[pix] + bias_g[c]) * scale; a null table entry = no noise / no bias for that instance
 int noise_bias_act_forward_g(float* y, const float* x, int G, const PtrTable& noise, const PtrTable& nw, const PtrTable& bias, int C, int HW,
                              float slope, float scale, hipStream_t s);
-// the same with a per-instance addend [C][HW] inside the activation: y = lrelu(x + addend_g + bias_g[c]) * scale (null entry: none)
-int bias_act_forward_addend_g(float* y, const float* x, int G, const PtrTable& addend, const PtrTable& bias, int C, int HW, float slope, float scale,
-                              hipStream_t s);
 // out[r] = sum of in[m] over the members m in [begin[r], begin[r + 1]) -- instances of n floats each, R <= kMaxGroups ranges
 int sum_member_ranges(float* out, const float* in, const int* begin, int R, long long n, hipStream_t s);
 // floats of `partials` the backward needs

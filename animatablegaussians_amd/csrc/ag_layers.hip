@@ -8,7 +8,6 @@
 #include "../../include/ag_layers.h"
 #include "../../include/ag_styleunet.h"
 
-#include <cstdlib>
 #include <cstring>
 
 using namespace ag;
@@ -50,14 +49,6 @@ bool geometry(const AgGroupedLayerArgs* a, Geo& g)
 size_t pad64(size_t n) { return (n + 63) / 64 * 64; }
 
 const ConvOpts kOihw = [] { ConvOpts o; o.wt_oihw = true; return o; }();
-
-// The activation pass (noise + bias + leaky ReLU) inside the convolution's epilogue wherever no Blur sits between the two (round 4: the
-// pre-activation tensor is neither written nor re-read).  AG_FUSED_ACT=0: the separate pass (same bits; same-box A/B, profiles/).
-bool fused_act()
-{
-    static const bool on = [] { const char* e = getenv("AG_FUSED_ACT"); return !(e && e[0] == '0'); }();
-    return on;
-}
 
 // float offsets of the regions inside `scratch`
 struct Scratch {
@@ -203,7 +194,9 @@ int ag_grouped_layer_forward(const AgGroupedLayerArgs* a, void* stream)
         ConvOpts o;
         o.packed = reinterpret_cast<float*>(a->packed_weights); o.packed_valid = packed_frozen;
         if ((rc = keep_maxima(w_t, cx, cx_gs, (long long)a->Cin * (a->resample ? g.BH * g.BW : a->H * a->W), o))) return rc;
-        if (fused_act() && !(a->k == 1 && a->Cin <= 4)) {       // (the 3-channel FromRGB convolutions run on the streaming 1 x 1 kernel, which has no such epilogue)
+        // the activation pass (bias + leaky ReLU) inside the convolution's epilogue: the pre-activation tensor is neither written nor re-read
+        // (same bits as the separate pass; DESIGN.md §4 names the A/B)
+        if (!(a->k == 1 && a->Cin <= 4)) {       // (the 3-channel FromRGB convolutions run on the streaming 1 x 1 kernel, which has no such epilogue)
             ConvAct act{ 1, a->slope, a->act_scale, PtrTable{}, PtrTable{} };
             if ((rc = zero_omax())) return rc;
             act.out_amax = omax;
@@ -240,22 +233,20 @@ int ag_grouped_layer_forward(const AgGroupedLayerArgs* a, void* stream)
         if (!a->k_blur) { set_error("ag_layer_forward: resampling layer without FIR taps"); return AG_ERR_INVALID_ARGUMENT; }
         if ((rc = conv_forward_g(&g.d, G, a->x, x_gs, wm_t, nullptr, PtrTable{}, aux, (long long)a->Cout * g.CH * g.CW, a->workspace, a->workspace_bytes, s, om))) return rc;
         // Blur + noise + bias + leaky ReLU in one pass (the backward needs the output only, so the blurred pre-activation is never stored)
-        if (fused_act() && G * a->Cout <= 65535 && (rc = zero_omax())) return rc;
-        if (fused_act() && G * a->Cout <= 65535)
-            return blur_act_forward_g(a->out, aux, a->k_blur, G, noise_t, nw_t, bias_t, a->Cout, g.CH, g.CW, a->slope, a->act_scale, s, omax);
-        if ((rc = ag_upfirdn2d(pre, aux, a->k_blur, G * a->Cout, g.CH, g.CW, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1, stream))) return rc;
-    } else {
-        if (fused_act()) {
-            ConvAct act{ 1, a->slope, a->act_scale, noise_t, nw_t };
+        if (G * a->Cout <= 65535) {
             if ((rc = zero_omax())) return rc;
-            act.out_amax = omax;
-            om.act = &act;
-            return conv_forward_g(&g.d, G, a->x, x_gs, wm_t, nullptr, bias_t, a->out, pre_gs, a->workspace, a->workspace_bytes, s, om);
+            return blur_act_forward_g(a->out, aux, a->k_blur, G, noise_t, nw_t, bias_t, a->Cout, g.CH, g.CW, a->slope, a->act_scale, s, omax);
         }
-        if ((rc = conv_forward_g(&g.d, G, a->x, x_gs, wm_t, nullptr, PtrTable{}, pre, pre_gs, a->workspace, a->workspace_bytes, s, om))) return rc;
+        if ((rc = ag_upfirdn2d(pre, aux, a->k_blur, G * a->Cout, g.CH, g.CW, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1, stream))) return rc;
+        if ((rc = noise_bias_act_forward_g(a->out, pre, G, noise_t, nw_t, bias_t, a->Cout, g.OH * g.OW, a->slope, a->act_scale, s))) return rc;
+        return sweep_out();
     }
-    if ((rc = noise_bias_act_forward_g(a->out, pre, G, noise_t, nw_t, bias_t, a->Cout, g.OH * g.OW, a->slope, a->act_scale, s))) return rc;
-    return sweep_out();
+    // noise + bias + leaky ReLU inside the convolution's epilogue
+    ConvAct act{ 1, a->slope, a->act_scale, noise_t, nw_t };
+    if ((rc = zero_omax())) return rc;
+    act.out_amax = omax;
+    om.act = &act;
+    return conv_forward_g(&g.d, G, a->x, x_gs, wm_t, nullptr, bias_t, a->out, pre_gs, a->workspace, a->workspace_bytes, s, om);
 }
 
 int ag_grouped_layer_backward(const AgGroupedLayerArgs* a, void* stream)
@@ -515,8 +506,7 @@ int ag_grouped_comb_forward(const AgGroupedCombArgs* a, void* stream)
     if (!comb_ok(a) || !a->x || !a->lev || !a->out || !a->scratch) { set_error("ag_grouped_comb_forward: bad arguments"); return AG_ERR_INVALID_ARGUMENT; }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long hw = (long long)a->H * a->W;
-    float* pre = a->scratch;
-    float* t = a->scratch + pad64((size_t)a->M * a->Cout * hw);
+    float* t = a->scratch + pad64((size_t)a->M * a->Cout * hw);      // (the region before it is the backward's: the pre-activation's gradient)
     ConvOpts o;
     o.w_cin_total = a->C1 + a->C2;
     PtrTable w1{}, w2{}, addend{}, bias = table_of(a->act_bias, a->M);
@@ -545,20 +535,11 @@ int ag_grouped_comb_forward(const AgGroupedCombArgs* a, void* stream)
     o2.packed = reinterpret_cast<float*>(a->packed_lev); o2.packed_valid = frozen;
     float* const omax = (conv_math_needs_absmax() && a->out_maxima) ? a->out_maxima : nullptr;
     if ((rc = conv_forward_g(&d2, a->N, a->lev, a->C2 * hw, w2, nullptr, PtrTable{}, t, a->Cout * hw, a->workspace, a->workspace_bytes, s, o2))) return rc;
-    if (fused_act()) {
-        ConvAct act{ 2, a->slope, a->act_scale, addend, PtrTable{} };
-        act.out_amax = omax;
-        ConvOpts oa = o1;
-        oa.act = &act;
-        return conv_forward_g(&d1, a->M, a->x, a->C1 * hw, w1, nullptr, bias, a->out, a->Cout * hw, a->workspace, a->workspace_bytes, s, oa);
-    }
-    if ((rc = conv_forward_g(&d1, a->M, a->x, a->C1 * hw, w1, nullptr, PtrTable{}, pre, a->Cout * hw, a->workspace, a->workspace_bytes, s, o1))) return rc;
-    if ((rc = bias_act_forward_addend_g(a->out, pre, a->M, addend, bias, a->Cout, (int)hw, a->slope, a->act_scale, s))) return rc;
-    if (omax) {
-        const AmaxTensor to{ a->out, nullptr, a->Cout * hw, a->Cout * hw, 0, 1 };
-        return conv_absmax(&to, 1, a->M, omax, s);
-    }
-    return AG_OK;
+    // the level half, the bias and the leaky ReLU inside the members' convolution epilogue (kind 2: the addend)
+    ConvAct act{ 2, a->slope, a->act_scale, addend, PtrTable{} };
+    act.out_amax = omax;
+    o1.act = &act;
+    return conv_forward_g(&d1, a->M, a->x, a->C1 * hw, w1, nullptr, bias, a->out, a->Cout * hw, a->workspace, a->workspace_bytes, s, o1);
 }
 
 int ag_grouped_comb_backward(const AgGroupedCombArgs* a, void* stream)

@@ -1,30 +1,25 @@
-"""Layer-level autograd nodes of the StyleUNet: ConvLayer, StyledConv and ToRGB (dual_styleunet.py:326-371, 570-604, 607-633) each as
-ONE ``torch.autograd.Function`` that runs the same kernels, in the same order, as the chain of per-kernel Functions in
-``styleunet_ops`` / ``conv`` -- so the results are bit-identical -- but costs autograd one node instead of three to six.
+"""The layer-level autograd nodes of the StyleUNet, one ``torch.autograd.Function`` per layer of dual_styleunet.py:
 
-Why: after the convolutions moved to the 16-bit matrix pipe (round 2) the training step was bound by the host (profiles/host_op_times.py: 1300
-custom-op calls per step, 13-32 us each inside their bodies plus autograd's own per-node bookkeeping).  The per-kernel Functions stay
-the single implementation of every kernel call: a fused node calls their ``forward`` / ``backward`` static methods as plain functions
-with a stand-in for autograd's ``ctx`` (``_Sub``), it does not duplicate them.
+  * ``_LayerCall``: ConvLayer (:326-371) and StyledConv (:570-604) as ONE native call each way (include/ag_layers.h ``AgLayerArgs``): the
+    kernel sequence is issued from C, so the host pays one Python -> ctypes transition, one output allocation and one argument check per
+    layer and direction instead of one per kernel (3-5 per layer, 13-32 us each; profiles/README.md has the host issue times).
+  * ``_ToRGB`` (:607-633): the per-kernel Functions of ``styleunet_ops`` / ``conv`` composed in Python.  It calls their ``forward`` /
+    ``backward`` static methods as plain functions with a stand-in for autograd's ``ctx`` (``_Sub``), it does not duplicate them; the wavelet
+    skip iwt -> Upsample -> dwt is the one composed kernel ``skip_chain``.
+
+``styleunet.set_fused_layers(False)`` runs the chain of per-kernel Functions instead; tests/test_styleunet_net.py pins the two against
+each other.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
+from . import _lib
 from . import conv as agc
-import os
-
-from .styleunet_ops import (_HAAR_ANALYSIS, _HAAR_SYNTHESIS, _Block2x2, _ModulateWeight, _NoiseBiasAct, _transpose4, _UpFirDn2d,
-                            skip_chain_backward, skip_chain_forward_)
-
-# ToRGB's iwt -> Upsample -> dwt skip path as one kernel (AG_SKIP_CHAIN=0: the three kernels + the addition, for the A/B and the equality test)
-_SKIP_CHAIN = os.environ.get("AG_SKIP_CHAIN") != "0"
-
-
-def set_skip_chain(on: bool) -> bool:
-    global _SKIP_CHAIN
-    prev, _SKIP_CHAIN = _SKIP_CHAIN, bool(on)
-    return prev
+from ._lib import scratch as _scratch, stream as _stream
+from .styleunet_ops import _flipped, _ModulateWeight, skip_chain_backward, skip_chain_forward_
 
 _SQRT2 = 2 ** 0.5
 
@@ -83,74 +78,6 @@ def _releasing(backward):
     return wrapped
 
 
-class _ConvLayer(torch.autograd.Function):
-    """[Blur] + EqualConv2d + FusedLeakyReLU(bias)."""
-
-    @staticmethod
-    def forward(ctx, x, w, bias, k_blur, scale, downsample):
-        s_blur = s_conv = None
-        k = int(w.shape[-1])
-        if downsample:
-            s_blur = _Sub()
-            x = _UpFirDn2d.forward(s_blur, x, k_blur, (1, 1), (1, 1), (2, 2, 2, 2))
-        s_conv = _Sub()
-        y = agc._Conv.forward(s_conv, x, w, None, None, agc.AG_CONV, 2 if downsample else 1, 0 if downsample else k // 2, scale)
-        s_act = _Sub()
-        out = _NoiseBiasAct.forward(s_act, y, None, None, bias, 0.2, _SQRT2)
-        _stash(ctx, (s_blur, s_conv, s_act))
-        return out
-
-    @staticmethod
-    @_releasing
-    def backward(ctx, g):
-        s_blur, s_conv, s_act = _unstash(ctx)
-        nx, nw, nb = ctx.needs_input_grad[:3]
-        s_act.needs_input_grad = (True, False, False, nb, False, False)
-        g, _, _, gb, _, _ = _NoiseBiasAct.backward(s_act, g)
-        s_conv.needs_input_grad = (nx, nw)
-        gx, gw = agc._Conv.backward(s_conv, g)[:2]
-        if s_blur is not None and gx is not None:
-            gx = _UpFirDn2d.backward(s_blur, gx)[0]
-        return gx, gw, gb, None, None, None
-
-
-class _StyledConv(torch.autograd.Function):
-    """ModulatedConv2d (modulate + demodulate the weight, [transposed] convolution, [blur]) + NoiseInjection + FusedLeakyReLU."""
-
-    @staticmethod
-    def forward(ctx, x, w, style, noise, noise_weight, act_bias, k_blur, mod_scale, upsample):
-        s_mod = _Sub()
-        wm = _ModulateWeight.forward(s_mod, w, style, mod_scale, True, upsample)
-        s_conv = _Sub()
-        s_blur = None
-        if upsample:
-            y = agc._Conv.forward(s_conv, x, wm, None, None, agc.AG_CONV_TRANSPOSE, 2, 0, 1.0)
-            s_blur = _Sub()
-            y = _UpFirDn2d.forward(s_blur, y, k_blur, (1, 1), (1, 1), (1, 1, 1, 1))
-        else:
-            y = agc._Conv.forward(s_conv, x, wm, None, None, agc.AG_CONV, 1, 1, 1.0)
-        s_act = _Sub()
-        out = _NoiseBiasAct.forward(s_act, y, noise, noise_weight if noise is not None else None, act_bias, 0.2, _SQRT2)
-        _stash(ctx, (s_mod, s_conv, s_blur, s_act))
-        return out
-
-    @staticmethod
-    @_releasing
-    def backward(ctx, g):
-        s_mod, s_conv, s_blur, s_act = _unstash(ctx)
-        nx, nw, ns, _, nnw, nb = ctx.needs_input_grad[:6]
-        s_act.needs_input_grad = (True, False, nnw, nb, False, False)
-        g, _, gnw, gb, _, _ = _NoiseBiasAct.backward(s_act, g)
-        if s_blur is not None:
-            g = _UpFirDn2d.backward(s_blur, g)[0]
-        s_conv.needs_input_grad = (nx, nw or ns)
-        gx, gwm = agc._Conv.backward(s_conv, g)[:2]
-        gw = gs = None
-        if gwm is not None:
-            gw, gs = _ModulateWeight.backward(s_mod, gwm)[:2]
-        return gx, gw, gs, None, gnw, gb, None, None, None
-
-
 class _ToRGB(torch.autograd.Function):
     """ToRGB: modulated 1 x 1 convolution (no demodulation) + bias [+ wavelet-domain upsampled skip: iwt -> Upsample -> dwt]."""
 
@@ -160,35 +87,22 @@ class _ToRGB(torch.autograd.Function):
         wm = _ModulateWeight.forward(s_mod, w, style, mod_scale, False, False)
         s_conv = _Sub()
         out = agc._Conv.forward(s_conv, x, wm, bias, None, agc.AG_CONV, 1, 0, 1.0)
-        s_up = None
         ctx.skip_k = None
-        if skip is not None:
-            if _SKIP_CHAIN:                                   # one kernel: the composed linear map, accumulated into the layer's output
-                skip_chain_forward_(out, skip, k_blur_up, accumulate=True)
-                ctx.skip_k = k_blur_up                        # a module buffer, not an output of this node: a plain attribute is safe
-            else:
-                s_m, s_u, s_s = _Sub(), _Sub(), _Sub()
-                t = _Block2x2.forward(s_m, skip, _HAAR_SYNTHESIS, True)
-                t = _UpFirDn2d.forward(s_u, t, k_blur_up, (2, 2), (1, 1), (2, 1, 2, 1))
-                out.add_(_Block2x2.forward(s_s, t, _HAAR_ANALYSIS, False))
-                s_up = s_u
-        _stash(ctx, (s_mod, s_conv, s_up))
+        if skip is not None:                                  # one kernel: the composed linear map, accumulated into the layer's output
+            skip_chain_forward_(out, skip, k_blur_up, accumulate=True)
+            ctx.skip_k = k_blur_up                            # a module buffer, not an output of this node: a plain attribute is safe
+        _stash(ctx, (s_mod, s_conv))
         return out
 
     @staticmethod
     @_releasing
     def backward(ctx, g):
-        s_mod, s_conv, s_up = _unstash(ctx)
+        s_mod, s_conv = _unstash(ctx)
         nx, nw, ns, nb, nskip = ctx.needs_input_grad[:5]
         g = g.contiguous()
         gskip = None
-        if ctx.skip_k is not None and nskip:                 # the fused skip path: one adjoint kernel
+        if ctx.skip_k is not None and nskip:                 # the skip path's adjoint: one kernel
             gskip = skip_chain_backward(g, ctx.skip_k)
-        elif s_up is not None and nskip:
-            # adjoints of the two fixed 2 x 2 block transforms: the other transform with the transposed matrix
-            t = _Block2x2.forward(_Sub(), g, _transpose4(_HAAR_ANALYSIS), True)
-            t = _UpFirDn2d.backward(s_up, t)[0]
-            gskip = _Block2x2.forward(_Sub(), t, _transpose4(_HAAR_SYNTHESIS), False)
         s_conv.needs_input_grad = (nx, nw or ns)
         s_conv.cfg = s_conv.cfg[:3] + (bool(nb),) + s_conv.cfg[4:]          # bias gradient only when the bias wants one
         gx, gwm, gb = agc._Conv.backward(s_conv, g)[:3]
@@ -198,25 +112,7 @@ class _ToRGB(torch.autograd.Function):
         return gx, gw, gs, gb, gskip, None, None
 
 
-# ---------------------------------------------------------------------------------------------------------------------------------
-# One NATIVE call per layer (include/ag_layers.h): the same kernel sequence issued from C.  The nodes above cost the host one
-# Python -> ctypes transition, one output allocation and one argument check per kernel (3-5 per layer and direction, 13-32 us each);
-# these cost one per layer.  AG_LAYER_CALLS=0 selects the nodes above (A/B, and the bit-equality test of the two paths).
-# ---------------------------------------------------------------------------------------------------------------------------------
-import ctypes  # noqa: E402
-import os  # noqa: E402
-
-from . import _lib  # noqa: E402
-from .styleunet_ops import _flipped  # noqa: E402
-
-_LAYER_CALLS = os.environ.get("AG_LAYER_CALLS") != "0"
 _SIZES = {}          # layer shape -> (OH, OW, forward scratch floats, backward scratch floats, conv workspace bytes)
-
-
-def set_layer_calls(on: bool) -> bool:
-    global _LAYER_CALLS
-    prev, _LAYER_CALLS = _LAYER_CALLS, bool(on)
-    return prev
 
 
 def _ptr(t):
@@ -230,17 +126,11 @@ def _layer_sizes(a):
         L = _lib.lib()
         oh, ow = ctypes.c_int32(0), ctypes.c_int32(0)
         _lib.check(L.ag_layer_output_size(ctypes.byref(a), ctypes.byref(oh), ctypes.byref(ow)), "ag_layer_output_size")
-        d = _lib.AgConvDesc()
-        d.Cin, d.Cout, d.k = a.Cin, a.Cout, a.k
-        if not a.modulated:
-            d.kind, d.H, d.W = agc.AG_CONV, a.H + (1 if a.resample else 0), a.W + (1 if a.resample else 0)
-            d.stride, d.padding = (2, 0) if a.resample else (1, a.k // 2)
-        else:
-            d.kind, d.H, d.W = (agc.AG_CONV_TRANSPOSE if a.resample else agc.AG_CONV), a.H, a.W
-            d.stride, d.padding = (2, 0) if a.resample else (1, a.k // 2)
-        d.weight_scale = 1.0
+        # the convolution workspace: the library maps the layer to its convolution (ag_layers.hip geometry()); the single-layer call is G = 1
+        g = _lib.AgGroupedLayerArgs()
+        g.G, g.Cin, g.Cout, g.H, g.W, g.k, g.resample, g.modulated = 1, a.Cin, a.Cout, a.H, a.W, a.k, a.resample, a.modulated
         v = _SIZES[key] = (oh.value, ow.value, int(L.ag_layer_scratch_floats(ctypes.byref(a), 0)), int(L.ag_layer_scratch_floats(ctypes.byref(a), 1)),
-                           int(L.ag_conv_workspace_bytes(ctypes.byref(d))))
+                           int(L.ag_grouped_layer_workspace_bytes(ctypes.byref(g))))
     return v
 
 
@@ -259,15 +149,6 @@ def _describe(x, w, k_blur, scale, resample, modulated):
     return a
 
 
-def _scratch(a, backward, dev):
-    """One buffer for the call's intermediates and the convolution workspace; returns (tensor, scratch pointer, workspace pointer, workspace bytes)."""
-    _, _, f_fwd, f_bwd, ws = _layer_sizes(a)
-    nfl = f_bwd if backward else f_fwd
-    buf = torch.empty(nfl * 4 + ws + 512, dtype=torch.uint8, device=dev)
-    base = (buf.data_ptr() + 255) & ~255
-    return buf, base, base + ((nfl * 4 + 255) & ~255), ws
-
-
 class _LayerCall(torch.autograd.Function):
     """ConvLayer (modulated = False: style / noise / noise_weight are None) or StyledConv as ONE native call each way."""
 
@@ -275,7 +156,7 @@ class _LayerCall(torch.autograd.Function):
     def forward(ctx, x, w, style, noise, noise_weight, bias, k_blur, scale, resample, modulated):
         x, w = x.contiguous(), w.contiguous()
         a = _describe(x, w, k_blur, scale, resample, modulated)
-        oh, ow = _layer_sizes(a)[:2]
+        oh, ow, f_fwd, _, a.workspace_bytes = _layer_sizes(a)
         dev = x.device
         out = torch.empty((1, a.Cout, oh, ow), dtype=torch.float32, device=dev)
         keep = None                                       # what the backward needs besides the inputs and the output
@@ -297,9 +178,9 @@ class _LayerCall(torch.autograd.Function):
             a.x_blur = keep.data_ptr()
         a.x, a.weight, a.out, a.act_bias = x.data_ptr(), w.data_ptr(), out.data_ptr(), _ptr(bias)
         a.k_blur = _ptr(k_blur) if resample else None
-        buf, a.scratch, a.workspace, a.workspace_bytes = _scratch(a, False, dev)
+        buf, a.scratch, a.workspace = _scratch(f_fwd, a.workspace_bytes, dev)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().ag_layer_forward(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "ag_layer_forward")
+            _lib.check(_lib.lib().ag_layer_forward(ctypes.byref(a), _stream(dev)), "ag_layer_forward")
         ctx.save_for_backward(x, w, style, noise, noise_weight, bias, out, keep, _flipped(k_blur) if resample else None)
         ctx.cfg = (float(scale), bool(resample), bool(modulated))
         return out
@@ -333,24 +214,21 @@ class _LayerCall(torch.autograd.Function):
             gb = gbn[:a.Cout] if a.want_bias else None
             gnw = gbn[a.Cout:] if a.want_noise_weight else None
         a.g_x, a.g_weight, a.g_style, a.g_bias_noise = _ptr(gx), _ptr(gw), _ptr(gs), _ptr(gbn)
-        buf, a.scratch, a.workspace, a.workspace_bytes = _scratch(a, True, dev)
+        _, _, _, f_bwd, a.workspace_bytes = _layer_sizes(a)
+        buf, a.scratch, a.workspace = _scratch(f_bwd, a.workspace_bytes, dev)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().ag_layer_backward(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "ag_layer_backward")
+            _lib.check(_lib.lib().ag_layer_backward(ctypes.byref(a), _stream(dev)), "ag_layer_backward")
         if gnw is not None and noise_weight is not None:
             gnw = gnw.view(noise_weight.shape)
         return gx, gw, gs, None, gnw, gb, None, None, None, None
 
 
 def conv_layer(x, w, bias, k_blur, scale, downsample):
-    if _LAYER_CALLS:
-        return _LayerCall.apply(x, w, None, None, None, bias, k_blur if downsample else None, float(scale), bool(downsample), False)
-    return _ConvLayer.apply(x, w, bias, k_blur, float(scale), bool(downsample))
+    return _LayerCall.apply(x, w, None, None, None, bias, k_blur if downsample else None, float(scale), bool(downsample), False)
 
 
 def styled_conv(x, w, style, noise, noise_weight, act_bias, k_blur, mod_scale, upsample):
-    if _LAYER_CALLS:
-        return _LayerCall.apply(x, w, style, noise, noise_weight, act_bias, k_blur if upsample else None, float(mod_scale), bool(upsample), True)
-    return _StyledConv.apply(x, w, style, noise, noise_weight, act_bias, k_blur, float(mod_scale), bool(upsample))
+    return _LayerCall.apply(x, w, style, noise, noise_weight, act_bias, k_blur if upsample else None, float(mod_scale), bool(upsample), True)
 
 
 def to_rgb(x, w, style, bias, skip, k_blur_up, mod_scale):

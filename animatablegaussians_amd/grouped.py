@@ -21,6 +21,7 @@ import os
 import torch
 
 from . import _lib
+from ._lib import scratch as _scratch, stream as _stream
 from . import conv as agc
 from .linear_ops import bilinear_resize, bilinear_resize_backward, plane_sums, select_add_rows
 from .styleunet import latents_of
@@ -37,10 +38,6 @@ def set_comb_split(on: bool) -> bool:
     global _COMB_SPLIT
     prev, _COMB_SPLIT = _COMB_SPLIT, bool(on)
     return prev
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 _INDEX = {}
@@ -213,12 +210,6 @@ def _merge_shared(stacked, owners, needs, view_shape=None):
             out.append(shaped(summed[slot[g]]))
         seen.add(slot[g])
     return out
-
-
-def _scratch(nfloats, ws_bytes, dev):
-    buf = torch.empty(nfloats * 4 + ws_bytes + 512, dtype=torch.uint8, device=dev)
-    base = (buf.data_ptr() + 255) & ~255
-    return buf, base, base + ((nfloats * 4 + 255) & ~255)
 
 
 class _GroupedLayer(torch.autograd.Function):
@@ -870,10 +861,9 @@ class GroupedStyleUNets:
 
     def _frozen_cache_for(self, styles):
         """The frozen-weight cache of this object (a dict the layer calls fill and read, see ``_FROZEN``) when the call is an inference call --
-        no autograd, no hipGraph capture, one stream -- and None otherwise.  It is emptied whenever a parameter or buffer of the networks, a style
+        no autograd, no hipGraph capture -- and None otherwise.  It is emptied whenever a parameter or buffer of the networks, a style
         input or the arithmetic mode has changed since it was filled (version counters; ``optim.FusedAdam`` bumps them like torch's optimizers)."""
-        if torch.is_grad_enabled() or not frozen_weights_enabled() or torch.cuda.is_current_stream_capturing() or \
-           int(os.environ.get("AG_GROUPED_STREAMS", "1")) != 1:
+        if torch.is_grad_enabled() or not frozen_weights_enabled() or torch.cuda.is_current_stream_capturing():
             return None
         # the tensor list is rebuilt on every call (a REPLACED Parameter object must be seen) and the token is a tuple, not a sum (sums of addresses
         # and versions can collide); a non-contiguous parameter or style would be cached under the address of a per-call temporary: no cache then
@@ -916,30 +906,7 @@ class GroupedStyleUNets:
                 raise ValueError(f"grouped networks: network {i} was given an empty list of views (pass None / omit it for no view features)")
         multi = {i: isinstance(v, (list, tuple)) and len(v) > 0 and isinstance(v[0], (list, tuple)) for i, v in view_features.items()}
         views = {i: (list(view_features[i]) if multi[i] else [view_features[i]]) for i in view_features}
-        # AG_GROUPED_STREAMS=2: the decoders as two chains (branch 1 / branch 2 of every network, G = 3 each) on two HIP streams
-        # instead of one chain with G = 6 -- twice the decoder launches, but the latency-bound layers at <= 32^2 overlap
-        nstreams = int(os.environ.get("AG_GROUPED_STREAMS", "1"))
-        if nstreams == 2 and not torch.cuda.is_current_stream_capturing() and os.environ.get("AG_SINGLE_STREAM") != "1":
-            cur = torch.cuda.current_stream()
-            if getattr(self, "_side", None) is None or self._side.device != cur.device:
-                self._side = torch.cuda.Stream(cur.device)
-                quiet = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None)
-                if quiet is not None:
-                    quiet(False)
-            side = self._side
-            side.wait_stream(cur)
-            shared = list(levels) + list(lat) + [f for vs in views.values() for fb in vs if fb is not None for f in fb if f is not None]
-            for t in shared:
-                t.record_stream(side)
-            with torch.cuda.stream(side):
-                r2 = self._decode([(i, 2) for i in range(len(nets))], lat, noises, levels, views)
-            results = self._decode([(i, 1) for i in range(len(nets))], lat, noises, levels, views)
-            cur.wait_stream(side)
-            for t in r2.values():
-                t.record_stream(cur)
-            results.update(r2)
-        else:
-            results = self._decode([(i, b) for i in range(len(nets)) for b in (1, 2)], lat, noises, levels, views)
+        results = self._decode([(i, b) for i in range(len(nets)) for b in (1, 2)], lat, noises, levels, views)
         outs = []
         for i in range(len(nets)):
             nv = len(views.get(i, [None]))

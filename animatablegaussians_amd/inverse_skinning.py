@@ -19,6 +19,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from ._lib import stream as _stream
 from .weight_volume import WeightVolume
 
 HAND_JOINTS = ((25, 40, 20), (40, 55, 21))        # joints [first, last) take the matrix of the wrist (template.py:213-214)
@@ -26,10 +27,6 @@ HAND_JOINTS = ((25, 40, 20), (40, 55, 21))        # joints [first, last) take th
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(None)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _points(t, name: str, dev=None, last: int = 3) -> torch.Tensor:

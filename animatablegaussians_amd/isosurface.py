@@ -71,7 +71,7 @@ def marching_cubes(volume: torch.Tensor, iso: float = 0.0, spacing=(1.0, 1.0, 1.
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     c_sp, c_org = (ctypes.c_float * 3)(*sp), (ctypes.c_float * 3)(*org)
     with _lib.on_device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         _lib.check(L.ag_isosurface_count(_ptr(vol), _ptr(m), X, Y, Z, iso, _ptr(ws), n_ws, _ptr(counts), stream), "ag_isosurface_count")
         V, F = (int(c) for c in counts.cpu())
         vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
@@ -92,7 +92,7 @@ def volume_normals(volume: torch.Tensor, voxel_size, grid_pts: torch.Tensor) -> 
     pts = grid_pts.to(torch.float32).contiguous()
     out = torch.empty((pts.shape[0], 3), dtype=torch.float32, device=dev)
     with _lib.on_device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         _lib.check(L.ag_weight_volume_gradient(_ptr(volume), X, Y, Z, 1, (ctypes.c_float * 3)(*_three(voxel_size, "voxel_size")), _ptr(grad), stream),
                    "ag_weight_volume_gradient")
         if pts.shape[0]:

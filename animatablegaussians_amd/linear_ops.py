@@ -10,12 +10,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from ._lib import stream as _stream
 
 MAX_JOBS = _lib.AG_LINEAR_MAX_JOBS
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check_gpu(t, what):

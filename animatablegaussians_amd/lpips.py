@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import stream as _stream
 from . import conv as agc
 from .styleunet_ops import noise_bias_act
 
@@ -37,10 +38,6 @@ CHNS = (64, 128, 256, 512, 512)
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class _MaxPool2x2(torch.autograd.Function):

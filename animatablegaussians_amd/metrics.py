@@ -98,7 +98,7 @@ def psnr_ssim_sums(pred: torch.Tensor, gt: torch.Tensor, *, data_range: float = 
         with _lib.on_device(dev):
             _lib.check(L.ag_psnr_ssim(_p(x), _p(y), B, H, W, C, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, cov_norm, C1, C2,
                                       _p(sq), _p(ss), _p(smap), _p(ws), ws.numel(),
-                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "ag_psnr_ssim")
+                                      _lib.stream(dev)), "ag_psnr_ssim")
     return sq, ss, H * W * C, (H - 2 * p) * (W - 2 * p) * C, smap
 
 

@@ -4,7 +4,8 @@ from __future__ import annotations
 import ctypes
 
 import numpy as np
-import torch
+
+from ._lib import stream  # noqa: F401  (the wrappers take it from here, with ptr)
 
 
 def pad(v: int, m: int) -> int:
@@ -34,7 +35,3 @@ def unpack_rows(packed: np.ndarray, Kp: int, Np: int) -> np.ndarray:
 def ptr(t) -> ctypes.c_void_p:
     """The device pointer of ``t``; NULL for None and for an empty tensor."""
     return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-
-
-def stream(dev) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

@@ -61,7 +61,7 @@ class FusedAdam(torch.optim.Optimizer):
             cached = self._calls.get(gi)
             if cached is None or len(cached) != n_calls:
                 cached = self._calls[gi] = [_lib.AgAdamArgs() for _ in range(n_calls)]
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _lib.stream(dev)
             with _lib.on_device(dev):
                 for ci, a in enumerate(cached):
                     c0 = ci * _lib.AG_ADAM_MAX_TENSORS

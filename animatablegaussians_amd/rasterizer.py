@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import stream as _stream_ptr
 
 NUM_CHANNELS = 3  # cuda_rasterizer/config.h:15
 
@@ -44,10 +45,6 @@ def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
     if t.dtype != torch.float32:
         raise RuntimeError(f"{name} must be float32, got {t.dtype}")
     return t.contiguous()
-
-
-def _stream_ptr(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class _on_device:

@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import stream as _stream
 
 # nose, reye, leye, rear, lear | LBigToe, LSmallToe, LHeel, RBigToe, RSmallToe, RHeel | left finger tips | right finger tips
 # (order of vertex_joint_selector.py:35-66 with use_hands and use_feet_keypoints)
@@ -41,10 +42,6 @@ _EXTRA_JOINT_VERTS = (9120, 9929, 9448, 616, 6, 5770, 5780, 8846, 8463, 8474, 86
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 @dataclass

@@ -26,14 +26,13 @@ import torch
 from . import conv as agc
 from . import fused_layers
 from . import linear_ops
-from .styleunet_ops import haar_merge, haar_split, modulate_weight, noise_bias_act, skip_chain, upfirdn2d_nchw
+from .styleunet_ops import haar_merge, modulate_weight, noise_bias_act, skip_chain, upfirdn2d_nchw
 
 _SQRT2 = 2 ** 0.5
 # ConvLayer / StyledConv / ToRGB as one autograd node each (fused_layers.py: same kernels, same order, bit-identical results, a third of
-# the autograd nodes) -- with one exception: ToRGB's skip path iwt -> Upsample -> dwt runs as ONE composed kernel by default
-# (AG_SKIP_CHAIN, fused_layers.set_skip_chain), which equals the three-kernel chain to 1e-6 of the largest value, not to the bit
-# (tests/test_styleunet_ops.py::test_skip_chain_*).  AG_UNFUSED_LAYERS=1 or set_fused_layers(False) runs the per-kernel chain (A/B and
-# the equality test).
+# the autograd nodes).  AG_UNFUSED_LAYERS=1 or set_fused_layers(False) runs the per-kernel chain (A/B and the equality test).  On both
+# paths ToRGB's skip iwt -> Upsample -> dwt is ONE composed kernel (styleunet_ops.skip_chain), which equals the three kernels to 1e-6 of
+# the largest value, not to the bit (tests/test_styleunet_ops.py::test_skip_chain_*).
 _FUSED_LAYERS = os.environ.get("AG_UNFUSED_LAYERS") != "1"
 
 
@@ -265,9 +264,6 @@ class DualStyleUNet(torch.nn.Module):
         # NoiseInjection (:301-311) + FusedLeakyReLU (:596) in one pass
         return noise_bias_act(x, noise, self._p(f"{prefix}.noise.weight"), self._p(f"{prefix}.activate.bias"))
 
-    def _haar_split(self, x):                                             # HaarTransform (:387-403), one kernel
-        return haar_split(x)
-
     def _haar_merge(self, x):                                             # InverseHaarTransform (:406-425), one kernel
         return haar_merge(x)
 
@@ -279,12 +275,7 @@ class DualStyleUNet(torch.nn.Module):
         weight = self._modulated_weight(f"{prefix}.conv", w_latent, False)
         out = agc.conv2d(x, weight, bias=self._p(f"{prefix}.bias").reshape(-1), stride=1, padding=0)   # bias in the conv epilogue
         if skip is not None:
-            if fused_layers._SKIP_CHAIN:
-                out = out + skip_chain(skip, self._k_blur_up)            # iwt -> Upsample -> dwt as one kernel
-            else:
-                s = self._haar_merge(skip)
-                s = upfirdn2d_nchw(s, self._k_blur_up, up=2, pad=(2, 1))     # Upsample (:32-50)
-                out = out + self._haar_split(s)
+            out = out + skip_chain(skip, self._k_blur_up)                # iwt -> Upsample (:32-50) -> dwt as one kernel
         return out
 
     def get_latent(self, z):
@@ -346,7 +337,6 @@ class DualStyleUNet(torch.nn.Module):
         """``shared``: tensors allocated on the current stream that branch 2 reads on the side stream (encoder levels, latent,
         shared decoder state): they are registered with the side stream so the caching allocator does not hand their memory
         out again while side-stream kernels -- forward now, backward later -- may still be reading it."""
-        import os
         cur = torch.cuda.current_stream()
         capturing = torch.cuda.is_current_stream_capturing()
         if os.environ.get("AG_SINGLE_STREAM") == "1" or (capturing and os.environ.get("AG_CAPTURE_BRANCHES") != "1"):

@@ -12,14 +12,11 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import stream as _stream
 
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check_input(t: torch.Tensor, name: str) -> None:

@@ -28,15 +28,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import stream as _stream
 from .avatar_ops import mask_to_pix
 
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _dev(t: torch.Tensor, name: str, dtype, cols: Optional[int] = None) -> torch.Tensor:

@@ -76,7 +76,7 @@ def _run(color, matte, kernel_size: int, profiles: bool, dev):
     p = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off) if t is not None else None  # noqa: E731
     with _lib.on_device(dev):
         _lib.check(_lib.lib().ag_prepare_targets(p(color), p(matte), V, H, W, int(kernel_size), p(color_f), p(mask), p(boundary),
-                                                 p(prof), p(prof, V * H), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                                                 p(prof), p(prof, V * H), _lib.stream(dev)),
                    "ag_prepare_targets")
     return color_f, mask, boundary, prof
 

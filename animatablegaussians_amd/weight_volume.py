@@ -101,7 +101,7 @@ def diffusion_operator(values: torch.Tensor, fixed: torch.Tensor, spacing) -> to
     out = torch.empty_like(v)
     with _lib.on_device(v.device):
         _lib.check(_lib.lib().ag_weight_diffuse_apply(_ptr(v), _ptr(m), X, Y, Z, J, w, _ptr(out),
-                                                      ctypes.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)), "ag_weight_diffuse_apply")
+                                                      _lib.stream(v.device)), "ag_weight_diffuse_apply")
     return out
 
 
@@ -159,7 +159,7 @@ def diffuse_weights(target: torch.Tensor, fixed: torch.Tensor, spacing, *, tol: 
         return torch.where(den > 0, (num / den.clamp_min(1e-300)).sqrt(), num.sqrt())
 
     with _lib.on_device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         _lib.check(L.ag_weight_diffuse_init(_ptr(t), _ptr(m), X, Y, Z, J, w, _ptr(x), _ptr(r), _ptr(p), _ptr(ap), _ptr(ws), n_ws, _ptr(bb), _ptr(rr),
                                             stream), "ag_weight_diffuse_init")
         bb_host = bb.double().cpu()
@@ -318,7 +318,7 @@ class WeightVolume:
         with _lib.on_device(p.device):
             _lib.check(_lib.lib().ag_weight_volume_sample(ctypes.c_void_p(volume.data_ptr()), X, Y, Z, C, ctypes.c_void_p(p.data_ptr()), n,
                                                           self._bounds_host if requires_scale else None, ctypes.c_void_p(out.data_ptr()),
-                                                          ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)),
+                                                          _lib.stream(p.device)),
                        "ag_weight_volume_sample")
         return out
 
@@ -358,7 +358,7 @@ class WeightVolume:
         out = torch.empty((X, Y, Z, J, 3), dtype=torch.float32, device=vol.device)
         with _lib.on_device(vol.device):
             _lib.check(_lib.lib().ag_weight_volume_gradient(_ptr(vol), X, Y, Z, J, self._spacing_host(), _ptr(out),
-                                                            ctypes.c_void_p(torch.cuda.current_stream(vol.device).cuda_stream)),
+                                                            _lib.stream(vol.device)),
                        "ag_weight_volume_gradient")
         return out
 

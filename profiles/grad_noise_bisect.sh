@@ -13,8 +13,7 @@ run() { # name, env...
 }
 run default
 run comb_split_off AG_COMB_SPLIT=0
-run fused_act_off AG_FUSED_ACT=0
-run both_off AG_COMB_SPLIT=0 AG_FUSED_ACT=0
+# (recorded result: profiles/r05_grad_bisect/; the two AG_FUSED_ACT=0 legs went with that switch -- the separate activation pass gave the same bits)
 run fp32_math AG_CONV_MATH=fp32
 python - "$OUT" <<'PY'
 import glob, os, re, sys
