@@ -16,7 +16,7 @@
 // 8 B + 4 B per instance once, instead of 6+ radix passes over 12 B pairs.
 #include <mutex>
 
-#include "ag_common.h"
+#include "ag_gauss_geom.h"
 
 namespace ag {
 
@@ -148,10 +148,9 @@ __global__ void __launch_bounds__(1024) tile_scan_kernel(int T, const uint32_t* 
 
 int launch_tile_scan(const AgRasterForwardArgs& a, hipStream_t s, uint32_t capacity, bool skip_large)
 {
-    const int gx = (a.W + kTileX - 1) / kTileX, gy = (a.H + kTileY - 1) / kTileY;
     char* ib = aligned_base(a.image_buffer);
     ImageLayout il((size_t)a.W, (size_t)a.H);
-    { ProfScope ps(AG_K_TILE_SCAN, s); hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, gx * gy,
+    { ProfScope ps(AG_K_TILE_SCAN, s); hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, tile_grid(a.W, a.H).T(),
                        reinterpret_cast<const uint32_t*>(ib + il.tile_count),
                        reinterpret_cast<uint32_t*>(ib + il.cursor),
                        reinterpret_cast<uint2*>(ib + il.ranges),
@@ -163,22 +162,6 @@ int launch_tile_scan(const AgRasterForwardArgs& a, hipStream_t s, uint32_t capac
 // ---------------------------------------------------------------------------------------------------------
 // 3. scatter: one thread per Gaussian, one (depth|index) key per touched tile
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void get_rect_i(float px, float py, int max_radius, int gx, int gy,
-                                           uint32_t& x0o, uint32_t& y0o, uint32_t& x1o, uint32_t& y1o)
-{
-    // identical to the preprocess kernel (auxiliary.h:46-56); only exact fp32 adds and a division by 16
-    const float r = (float)max_radius;
-    int x0 = (int)((px - r) / (float)kTileX);
-    int y0 = (int)((py - r) / (float)kTileY);
-    int x1 = (int)((px + r + (float)kTileX - 1.0f) / (float)kTileX);
-    int y1 = (int)((py + r + (float)kTileY - 1.0f) / (float)kTileY);
-    x0 = max(0, x0); y0 = max(0, y0); x1 = max(0, x1); y1 = max(0, y1);
-    x0o = (uint32_t)min(gx, x0); y0o = (uint32_t)min(gy, y0);
-    x1o = (uint32_t)min(gx, x1); y1o = (uint32_t)min(gy, y1);
-}
-
-constexpr int kWinBins = 2048;   // same workgroup tile window as the preprocess kernel
-
 __global__ void __launch_bounds__(256) scatter_kernel(int P, int gx, int gy, const int* __restrict__ radii,
                                                      const GaussRec* __restrict__ rec, uint32_t* __restrict__ cursor,
                                                      uint64_t* __restrict__ keys, const uint32_t* __restrict__ counts)
@@ -192,18 +175,18 @@ __global__ void __launch_bounds__(256) scatter_kernel(int P, int gx, int gy, con
     __shared__ uint32_t s_hist[kWinBins];
     __shared__ uint32_t s_base[kWinBins];
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (threadIdx.x == 0) { s_win[0] = 0x7fffffff; s_win[1] = 0x7fffffff; s_win[2] = 0; s_win[3] = 0; }
+    if (threadIdx.x == 0) window_reset(s_win);
     __syncthreads();
-    uint32_t x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    TileRect rect = { 0, 0, 0, 0 };
     uint64_t key = 0;
     const int rad = (idx < P) ? radii[idx] : 0;
     if (rad > 0) {
         const float px = rec[idx].x, py = rec[idx].y;
         const uint32_t dbits = __float_as_uint(rec[idx].depth);
-        get_rect_i(px, py, rad, gx, gy, x0, y0, x1, y1);
+        rect = tile_rect(px, py, rad, gx, gy);
         key = ((uint64_t)dbits << 32) | (uint32_t)idx;
     }
-    window_accumulate(s_win, x1 > x0 && y1 > y0, (int)x0, (int)y0, (int)x1, (int)y1);
+    window_accumulate(s_win, rect.x1 > rect.x0 && rect.y1 > rect.y0, rect);
     __syncthreads();
     const int wx0 = s_win[0], wy0 = s_win[1];
     const int bw = s_win[2] - wx0, bh = s_win[3] - wy0;
@@ -212,24 +195,24 @@ __global__ void __launch_bounds__(256) scatter_kernel(int P, int gx, int gy, con
     if (nb <= kWinBins) {
         for (int i = threadIdx.x; i < nb; i += 256) s_hist[i] = 0u;
         __syncthreads();
-        for (uint32_t y = y0; y < y1; y++)
-            for (uint32_t x = x0; x < x1; x++) atomicAdd(&s_hist[((int)y - wy0) * bw + ((int)x - wx0)], 1u);
+        for (uint32_t y = rect.y0; y < rect.y1; y++)
+            for (uint32_t x = rect.x0; x < rect.x1; x++) atomicAdd(&s_hist[window_bin(wx0, wy0, bw, x, y)], 1u);
         __syncthreads();
         for (int i = threadIdx.x; i < nb; i += 256) {
             const uint32_t c = s_hist[i];
-            if (c) s_base[i] = atomicAdd(&cursor[(uint32_t)(wy0 + i / bw) * (uint32_t)gx + (uint32_t)(wx0 + i % bw)], c);
+            if (c) s_base[i] = atomicAdd(&cursor[window_tile(wx0, wy0, bw, gx, i)], c);
             s_hist[i] = 0u;
         }
         __syncthreads();
-        for (uint32_t y = y0; y < y1; y++)
-            for (uint32_t x = x0; x < x1; x++) {
-                const int li = ((int)y - wy0) * bw + ((int)x - wx0);
+        for (uint32_t y = rect.y0; y < rect.y1; y++)
+            for (uint32_t x = rect.x0; x < rect.x1; x++) {
+                const int li = window_bin(wx0, wy0, bw, x, y);
                 const uint32_t r = atomicAdd(&s_hist[li], 1u);
                 keys[s_base[li] + r] = key;
             }
     } else {
-        for (uint32_t y = y0; y < y1; y++)
-            for (uint32_t x = x0; x < x1; x++) {
+        for (uint32_t y = rect.y0; y < rect.y1; y++)
+            for (uint32_t x = rect.x0; x < rect.x1; x++) {
                 const uint32_t pos = atomicAdd(&cursor[y * (uint32_t)gx + x], 1u);
                 keys[pos] = key;
             }
@@ -473,7 +456,7 @@ __global__ void __launch_bounds__(NT) tile_sort_kernel(const uint4* __restrict__
 
 int launch_bin_sort(const AgRasterForwardArgs& a, int R, hipStream_t s, bool skip_large)
 {
-    const int gx = (a.W + kTileX - 1) / kTileX, gy = (a.H + kTileY - 1) / kTileY;
+    const TileGrid tg = tile_grid(a.W, a.H);
     if (R <= 0) return AG_OK;
     char* gb = aligned_base(a.geom_buffer);
     char* ib = aligned_base(a.image_buffer);
@@ -483,7 +466,7 @@ int launch_bin_sort(const AgRasterForwardArgs& a, int R, hipStream_t s, bool ski
     BinLayout bl((size_t)R);
     uint64_t* keys = reinterpret_cast<uint64_t*>(bb + bl.keys);
     uint32_t* point_list = reinterpret_cast<uint32_t*>(bb + bl.point_list);
-    { ProfScope ps(AG_K_SCATTER, s); hipLaunchKernelGGL(scatter_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, a.P, gx, gy, a.radii,
+    { ProfScope ps(AG_K_SCATTER, s); hipLaunchKernelGGL(scatter_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, a.P, tg.gx, tg.gy, a.radii,
                        reinterpret_cast<const GaussRec*>(gb + gl.rec), reinterpret_cast<uint32_t*>(ib + il.cursor), keys,
                        reinterpret_cast<const uint32_t*>(ib + il.num_rendered)); }
     if (check_hip(hipGetLastError(), "scatter_kernel")) return AG_ERR_HIP;
@@ -506,7 +489,7 @@ int launch_bin_sort(const AgRasterForwardArgs& a, int R, hipStream_t s, bool ski
         ProfScope ps(AG_K_TILE_SORT, s);
         const uint4* order = reinterpret_cast<const uint4*>(ib + il.tile_order);
         const uint32_t* counts = reinterpret_cast<const uint32_t*>(ib + il.num_rendered);
-        const int T = gx * gy;
+        const int T = tg.T();
         hipLaunchKernelGGL((tile_sort_kernel<512, false, 4>), dim3(T < 1280 ? T : 1280), dim3(512), kSmallLds, s, order, counts, keys, point_list);
         // the large class (tiles of 2049 .. 8192 instances merged from their sorted chunks, longer ones sorted in global memory): 256 workgroups
         // that each need a whole CU's LDS.  On avatar views no tile is that long and the launch was 4 us of the one-stream view and a 27-us slot

@@ -26,7 +26,7 @@
 //   * ds_add_f32 is a SERIAL unit on gfx950: 194 cycles per wave instruction whatever the address pattern, so lanes that hold DIFFERENT
 //     splats cannot sum through LDS float atomics;
 //   * one lane per pixel is 2.2 waves per SIMD on the bench view, each a dependent chain per entry: the SIMDs idle.
-#include "ag_common.h"
+#include "ag_gauss_geom.h"
 
 namespace ag {
 
@@ -409,9 +409,8 @@ int launch_blend_backward(const AgRasterBackwardArgs& a, hipStream_t s)
 {
     BlendBwdParams p;
     p.W = a.W; p.H = a.H;
-    p.gx = (a.W + kTileX - 1) / kTileX;
-    const int gy = (a.H + kTileY - 1) / kTileY;
-    p.T = p.gx * gy;
+    const TileGrid tg = tile_grid(a.W, a.H);
+    p.gx = tg.gx; p.T = tg.T();
     const char* gb = aligned_base(a.geom_buffer);
     const char* ib = aligned_base(a.image_buffer);
     GeomLayout gl((size_t)a.P);

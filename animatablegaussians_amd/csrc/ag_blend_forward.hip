@@ -29,7 +29,7 @@
 // travels with the record.  Results differ from a serial evaluation only by the association of the transmittance
 // product (a few ulp).
 // Bound: VALU + LDS; HBM traffic is the compulsory 52 B/instance (x8 regions, served by L2) + 24 B/pixel.
-#include "ag_common.h"
+#include "ag_gauss_geom.h"
 
 namespace ag {
 
@@ -353,8 +353,8 @@ blend_forward_kernel(int W, int H, int gx, int n_tiles, const uint32_t* __restri
 
 int launch_blend_forward(const AgRasterForwardArgs& a, int R, hipStream_t s)
 {
-    const int gx = (a.W + kTileX - 1) / kTileX, gy = (a.H + kTileY - 1) / kTileY;
-    const int n_tiles = gx * gy;
+    const TileGrid tg = tile_grid(a.W, a.H);
+    const int gx = tg.gx, n_tiles = tg.T();
     char* gb = aligned_base(a.geom_buffer);
     char* ib = aligned_base(a.image_buffer);
     GeomLayout gl((size_t)a.P);

@@ -5,70 +5,25 @@
 // (Gaussian, tile) instance).  The tile-major counts make the later binning a counting sort by tile, so no
 // device-wide 64-bit radix sort is needed (see ag_binning.hip).
 //
-// THIS TRANSLATION UNIT IS COMPILED WITH -ffp-contract=off: the fp32 expression order below is the contract that
+// THIS TRANSLATION UNIT IS COMPILED WITH -ffp-contract=off: the fp32 expression order below and in ag_gauss_geom.h is the contract that
 // makes radii / tile rects / depth keys bit-identical to the CPU oracle (oracle/raster_oracle.c), which in turn
 // restates the reference's expression order (GLM column-major mat3 products, left-to-right sums).
 // HBM-bound streaming kernel: 44 B in, 48 B record + 24 B cov3D + 8 B out per Gaussian.
-#include "ag_common.h"
+#include "ag_gauss_geom.h"
 #include "ag_sh.h"
 
 namespace ag {
-
-struct M3 { float m[3][3]; };  // m[col][row], GLM convention
-
-__device__ __forceinline__ M3 m3_cols(float a, float b, float c, float d, float e, float f, float g, float h, float i)
-{
-    M3 r;
-    r.m[0][0] = a; r.m[0][1] = b; r.m[0][2] = c;
-    r.m[1][0] = d; r.m[1][1] = e; r.m[1][2] = f;
-    r.m[2][0] = g; r.m[2][1] = h; r.m[2][2] = i;
-    return r;
-}
-
-__device__ __forceinline__ M3 m3_mul(const M3& a, const M3& b)
-{
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int q = 0; q < 3; q++)
-            r.m[c][q] = a.m[0][q] * b.m[c][0] + a.m[1][q] * b.m[c][1] + a.m[2][q] * b.m[c][2];
-    return r;
-}
-
-__device__ __forceinline__ M3 m3_t(const M3& a)
-{
-    M3 r;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int q = 0; q < 3; q++) r.m[c][q] = a.m[q][c];
-    return r;
-}
 
 __device__ __forceinline__ float ndc2pix(float v, int S)
 {
     return (float)((((double)v + 1.0) * (double)S - 1.0) * 0.5);
 }
 
-__device__ __forceinline__ void get_rect(float px, float py, int max_radius, int gx, int gy,
-                                         uint32_t& x0o, uint32_t& y0o, uint32_t& x1o, uint32_t& y1o)
-{
-    const float r = (float)max_radius;
-    int x0 = (int)((px - r) / (float)kTileX);
-    int y0 = (int)((py - r) / (float)kTileY);
-    int x1 = (int)((px + r + (float)kTileX - 1.0f) / (float)kTileX);
-    int y1 = (int)((py + r + (float)kTileY - 1.0f) / (float)kTileY);
-    x0 = max(0, x0); y0 = max(0, y0); x1 = max(0, x1); y1 = max(0, y1);
-    x0o = (uint32_t)min(gx, x0); y0o = (uint32_t)min(gy, y0);
-    x1o = (uint32_t)min(gx, x1); y1o = (uint32_t)min(gy, y1);
-}
-
-constexpr int kWinBins = 2048;   // tile-window histogram bins per workgroup (8 KiB of LDS)
-
 struct PreParams {
     int P, W, H, gx, gy;
-    float tan_fovx, tan_fovy, focal_x, focal_y, scale_modifier;
+    float tan_fovx, tan_fovy;
+    Focal focal;
+    float scale_modifier;
     const float* __restrict__ means3D;
     const float* __restrict__ scales;
     const float* __restrict__ rotations;
@@ -94,7 +49,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
     // their tile rects fall into a small window of the tile grid.  Instances are counted with LDS atomics inside that
     // window and flushed with ONE global atomic per (workgroup, tile): ~20x fewer same-address global atomics than
     // one per instance (which serialise in L2 at ~5 M/s per address and cost 190 us at avatar scale).
-    __shared__ int s_win[4];             // min x, min y, max x, max y (tile units, max exclusive)
+    __shared__ int s_win[4];
     __shared__ uint32_t s_hist[kWinBins];
     // The 48-byte records and the 24-byte covariances leave through LDS: a thread's own record would be 12 + 6 dword stores at a
     // 48 / 24-byte lane stride (every store instruction touches 24 cache lines); staged, the workgroup writes its 12 + 6 KB as 16-byte
@@ -104,7 +59,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
     __shared__ __attribute__((aligned(16))) float s_rec[256 * 12];
     __shared__ __attribute__((aligned(16))) float s_cov[256 * 6];
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (threadIdx.x == 0) { s_win[0] = 0x7fffffff; s_win[1] = 0x7fffffff; s_win[2] = 0; s_win[3] = 0; }
+    if (threadIdx.x == 0) window_reset(s_win);
     __syncthreads();
 
     // wave-uniform camera: scalar loads
@@ -115,19 +70,17 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
     int my_radii = 0;
     bool cov_set = false, rec_set = false;
     uint32_t touched = 0;
-    uint32_t rx0 = 0, ry0 = 0, rx1 = 0, ry1 = 0;
+    TileRect rect = { 0, 0, 0, 0 };
     const bool valid = idx < p.P;
     const int sidx = valid ? idx : 0;
     const float ox = p.means3D[3 * sidx + 0], oy = p.means3D[3 * sidx + 1], oz = p.means3D[3 * sidx + 2];
 
     // near-plane cull only (auxiliary.h:154)
-    const float vz = V[2] * ox + V[6] * oy + V[10] * oz + V[14];
-    if (valid && vz > 0.2f) {
-        const float hx = Pm[0] * ox + Pm[4] * oy + Pm[8] * oz + Pm[12];
-        const float hy = Pm[1] * ox + Pm[5] * oy + Pm[9] * oz + Pm[13];
-        const float hw = Pm[3] * ox + Pm[7] * oy + Pm[11] * oz + Pm[15];
-        const float p_w = 1.0f / (hw + 0.0000001f);
-        const float projx = hx * p_w, projy = hy * p_w;
+    const float vz = view_depth(V, ox, oy, oz);
+    if (valid && beyond_near_plane(vz)) {
+        const float2 hp = homog_xy(Pm, ox, oy, oz);
+        const float p_w = homog_inv_w(Pm, ox, oy, oz);
+        const float projx = hp.x * p_w, projy = hp.y * p_w;
 
         float c3[6];
         if (p.cov3D_precomp) {
@@ -135,18 +88,9 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
             for (int k = 0; k < 6; k++) c3[k] = p.cov3D_precomp[6 * idx + k];
         } else {
             // computeCov3D, forward.cu:116-152 — quaternion used un-normalised
-            const float mod = p.scale_modifier;
-            M3 S = m3_cols(1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f);
-            S.m[0][0] = mod * p.scales[3 * idx + 0];
-            S.m[1][1] = mod * p.scales[3 * idx + 1];
-            S.m[2][2] = mod * p.scales[3 * idx + 2];
-            const float r = p.rotations[4 * idx + 0], x = p.rotations[4 * idx + 1];
-            const float y = p.rotations[4 * idx + 2], z = p.rotations[4 * idx + 3];
-            const M3 R = m3_cols(
-                1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
-                2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x),
-                2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y));
-            const M3 M = m3_mul(S, R);
+            const float3 s = modified_scale(p.scale_modifier, p.scales + 3 * idx);
+            const float* q = p.rotations + 4 * idx;
+            const M3 M = scaled_rotation(s, raw_quat_rotation(q[0], q[1], q[2], q[3]));
             const M3 Sigma = m3_mul(m3_t(M), M);
             c3[0] = Sigma.m[0][0]; c3[1] = Sigma.m[0][1]; c3[2] = Sigma.m[0][2];
             c3[3] = Sigma.m[1][1]; c3[4] = Sigma.m[1][2]; c3[5] = Sigma.m[2][2];
@@ -156,22 +100,18 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
         cov_set = true;
 
         // computeCov2D, forward.cu:74-113
-        float tx = V[0] * ox + V[4] * oy + V[8] * oz + V[12];
-        float ty = V[1] * ox + V[5] * oy + V[9] * oz + V[13];
-        const float tz = vz;
+        // The clamp is frustum_clamp of ag_gauss_geom.h, written out: called from there, the negation of J's -(focal t) / tz^2 entries is
+        // folded into the clamp instead of into tz and 98 of the unit's 1590 instructions are scheduled differently.
+        // Keep the two equal.
+        const float3 t = view_point(V, ox, oy, oz);
+        float tx = t.x, ty = t.y;
+        const float tz = t.z;
         const float limx = 1.3f * p.tan_fovx, limy = 1.3f * p.tan_fovy;
         const float txtz = tx / tz, tytz = ty / tz;
         tx = fminf(limx, fmaxf(-limx, txtz)) * tz;
         ty = fminf(limy, fmaxf(-limy, tytz)) * tz;
-        const M3 J = m3_cols(
-            p.focal_x / tz, 0.0f, -(p.focal_x * tx) / (tz * tz),
-            0.0f, p.focal_y / tz, -(p.focal_y * ty) / (tz * tz),
-            0.f, 0.f, 0.f);
-        const M3 Wm = m3_cols(V[0], V[4], V[8], V[1], V[5], V[9], V[2], V[6], V[10]);
-        const M3 T = m3_mul(Wm, J);
-        const M3 Vrk = m3_cols(c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]);
-        const M3 cov = m3_mul(m3_mul(m3_t(T), m3_t(Vrk)), T);
-        const float cxx = cov.m[0][0] + 0.3f, cxy = cov.m[0][1], cyy = cov.m[1][1] + 0.3f;
+        const Cov2D cov = project_cov(V, p.focal, tx, ty, tz, c3);
+        const float cxx = cov.xx, cxy = cov.xy, cyy = cov.yy;
 
         const float det = (cxx * cyy - cxy * cxy);
         if (det != 0.0f) {
@@ -182,9 +122,8 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
             const float lambda2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
             const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
             const float px = ndc2pix(projx, p.W), py = ndc2pix(projy, p.H);
-            uint32_t x0, y0, x1, y1;
-            get_rect(px, py, (int)my_radius, p.gx, p.gy, x0, y0, x1, y1);
-            const uint32_t n = (x1 - x0) * (y1 - y0);
+            const TileRect tr = tile_rect(px, py, (int)my_radius, p.gx, p.gy);
+            const uint32_t n = (tr.x1 - tr.x0) * (tr.y1 - tr.y0);
             if (n != 0) {
                 my_radii = (int)my_radius;
                 touched = n;
@@ -220,7 +159,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
                 g.qcut = qc;
                 *reinterpret_cast<GaussRec*>(s_rec + 12 * threadIdx.x) = g;
                 rec_set = true;
-                rx0 = x0; ry0 = y0; rx1 = x1; ry1 = y1;
+                rect = tr;
             }
         }
     }
@@ -237,7 +176,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
 #pragma unroll
         for (int k = 0; k < 6; k++) s_cov[6 * threadIdx.x + k] = 0.f;
     }
-    window_accumulate(s_win, touched != 0, (int)rx0, (int)ry0, (int)rx1, (int)ry1);
+    window_accumulate(s_win, touched != 0, rect);
     __syncthreads();
     {
         const int first = blockIdx.x * 256, nv = min(256, p.P - first);          // Gaussians of this workgroup
@@ -265,17 +204,17 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreParams p)
     if (nb <= kWinBins) {
         for (int i = threadIdx.x; i < nb; i += 256) s_hist[i] = 0u;
         __syncthreads();
-        for (uint32_t y = ry0; y < ry1; y++)
-            for (uint32_t x = rx0; x < rx1; x++) atomicAdd(&s_hist[((int)y - wy0) * bw + ((int)x - wx0)], 1u);
+        for (uint32_t y = rect.y0; y < rect.y1; y++)
+            for (uint32_t x = rect.x0; x < rect.x1; x++) atomicAdd(&s_hist[window_bin(wx0, wy0, bw, x, y)], 1u);
         __syncthreads();
         for (int i = threadIdx.x; i < nb; i += 256) {
             const uint32_t c = s_hist[i];
-            if (c) atomicAdd(&p.tile_count[(uint32_t)(wy0 + i / bw) * (uint32_t)p.gx + (uint32_t)(wx0 + i % bw)], c);
+            if (c) atomicAdd(&p.tile_count[window_tile(wx0, wy0, bw, p.gx, i)], c);
         }
     } else {
         // spatially incoherent input (e.g. randomly ordered Gaussians): plain per-instance atomics
-        for (uint32_t y = ry0; y < ry1; y++)
-            for (uint32_t x = rx0; x < rx1; x++) atomicAdd(&p.tile_count[y * (uint32_t)p.gx + x], 1u);
+        for (uint32_t y = rect.y0; y < rect.y1; y++)
+            for (uint32_t x = rect.x0; x < rect.x1; x++) atomicAdd(&p.tile_count[y * (uint32_t)p.gx + x], 1u);
     }
 }
 
@@ -283,11 +222,10 @@ int launch_preprocess(const AgRasterForwardArgs& a, hipStream_t s)
 {
     PreParams p;
     p.P = a.P; p.W = a.W; p.H = a.H;
-    p.gx = (a.W + kTileX - 1) / kTileX;
-    p.gy = (a.H + kTileY - 1) / kTileY;
+    const TileGrid tg = tile_grid(a.W, a.H);
+    p.gx = tg.gx; p.gy = tg.gy;
     p.tan_fovx = a.tan_fovx; p.tan_fovy = a.tan_fovy;
-    p.focal_y = a.H / (2.0f * a.tan_fovy);   // rasterizer_impl.cu:223-224
-    p.focal_x = a.W / (2.0f * a.tan_fovx);
+    p.focal = focal_lengths(a.W, a.H, a.tan_fovx, a.tan_fovy);
     p.scale_modifier = a.scale_modifier;
     p.means3D = a.means3D; p.scales = a.scales; p.rotations = a.rotations; p.opacities = a.opacities;
     p.colors = a.colors_precomp; p.cov3D_precomp = a.cov3D_precomp;
@@ -303,8 +241,7 @@ int launch_preprocess(const AgRasterForwardArgs& a, hipStream_t s)
     p.tiles_touched = reinterpret_cast<uint32_t*>(gb + gl.tiles_touched);
     p.clamped = reinterpret_cast<uint8_t*>(gb + gl.clamped);
     p.tile_count = reinterpret_cast<uint32_t*>(ib + il.tile_count);
-    const size_t T = (size_t)p.gx * p.gy;
-    if (check_hip(hipMemsetAsync(p.tile_count, 0, T * sizeof(uint32_t), s), "memset tile_count")) return AG_ERR_HIP;
+    if (check_hip(hipMemsetAsync(p.tile_count, 0, (size_t)tg.T() * sizeof(uint32_t), s), "memset tile_count")) return AG_ERR_HIP;
     { ProfScope ps(AG_K_PREPROCESS, s); hipLaunchKernelGGL(preprocess_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, p); }
     return check_hip(hipGetLastError(), "preprocess_kernel");
 }
@@ -315,8 +252,8 @@ __global__ void __launch_bounds__(256) mark_visible_kernel(int P, const float* _
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= P) return;
     const float ox = means3D[3 * idx + 0], oy = means3D[3 * idx + 1], oz = means3D[3 * idx + 2];
-    const float vz = view[2] * ox + view[6] * oy + view[10] * oz + view[14];
-    present[idx] = (vz <= 0.2f) ? 0 : 1;
+    const float vz = view_depth(view, ox, oy, oz);
+    present[idx] = (vz <= kNearPlane) ? 0 : 1;      // auxiliary.h:154 as written: a NaN depth counts as present
 }
 
 int launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s)

@@ -14,46 +14,15 @@
 // Semantics kept from the reference: the 1.3*tanfov clamp zeroes dL/dt.x, dL/dt.y outside the frustum guard
 // (:168-176), denom2inv = 1/(denom^2 + 1e-7) (:203), p_w = 1/(w + 1e-7) (:376), the depth gradient enters through
 // view-matrix row 2 (:391-403), the quaternion gradient is w.r.t. the RAW (un-normalised) quaternion (:340).
-#include "ag_common.h"
+#include "ag_gauss_geom.h"
 #include "ag_sh.h"
 
 namespace ag {
 
-struct M3b { float m[3][3]; };  // m[col][row], GLM convention
-
-__device__ __forceinline__ M3b mb_cols(float a, float b, float c, float d, float e, float f, float g, float h, float i)
-{
-    M3b r;
-    r.m[0][0] = a; r.m[0][1] = b; r.m[0][2] = c;
-    r.m[1][0] = d; r.m[1][1] = e; r.m[1][2] = f;
-    r.m[2][0] = g; r.m[2][1] = h; r.m[2][2] = i;
-    return r;
-}
-
-__device__ __forceinline__ M3b mb_mul(const M3b& a, const M3b& b)
-{
-    M3b r;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int q = 0; q < 3; q++)
-            r.m[c][q] = a.m[0][q] * b.m[c][0] + a.m[1][q] * b.m[c][1] + a.m[2][q] * b.m[c][2];
-    return r;
-}
-
-__device__ __forceinline__ M3b mb_t(const M3b& a)
-{
-    M3b r;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int q = 0; q < 3; q++) r.m[c][q] = a.m[q][c];
-    return r;
-}
-
 struct PreBwdParams {
     int P;
-    float h_x, h_y, tan_fovx, tan_fovy, scale_modifier;
+    Focal focal;
+    float tan_fovx, tan_fovy, scale_modifier;
     const float* __restrict__ means3D;
     const int* __restrict__ radii;
     const float* __restrict__ scales;
@@ -160,29 +129,20 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(PreBwdParams p
         for (int k = 0; k < 6; k++) c3[k] = s_c3[6 * tid + k];
 
         // ---- cov2D backward (backward.cu:144-274) ----
-        float tx = V[0] * mx + V[4] * my + V[8] * mz + V[12];
-        float ty = V[1] * mx + V[5] * my + V[9] * mz + V[13];
-        const float tz = V[2] * mx + V[6] * my + V[10] * mz + V[14];
-        const float limx = 1.3f * p.tan_fovx, limy = 1.3f * p.tan_fovy;
-        const float txtz = tx / tz, tytz = ty / tz;
-        tx = fminf(limx, fmaxf(-limx, txtz)) * tz;
-        ty = fminf(limy, fmaxf(-limy, tytz)) * tz;
-        const float x_grad_mul = (txtz < -limx || txtz > limx) ? 0.f : 1.f;
-        const float y_grad_mul = (tytz < -limy || tytz > limy) ? 0.f : 1.f;
+        const float3 t = view_point(V, mx, my, mz);
+        const FrustumClamp fc = frustum_clamp(t, p.tan_fovx, p.tan_fovy);
+        const float tx = fc.tx, ty = fc.ty, tz = t.z;
+        const float x_grad_mul = (fc.txtz < -fc.limx || fc.txtz > fc.limx) ? 0.f : 1.f;
+        const float y_grad_mul = (fc.tytz < -fc.limy || fc.tytz > fc.limy) ? 0.f : 1.f;
 
-        const M3b J = mb_cols(p.h_x / tz, 0.0f, -(p.h_x * tx) / (tz * tz),
-                              0.0f, p.h_y / tz, -(p.h_y * ty) / (tz * tz),
-                              0.f, 0.f, 0.f);
-        const M3b Wm = mb_cols(V[0], V[4], V[8], V[1], V[5], V[9], V[2], V[6], V[10]);
-        const M3b Vrk = mb_cols(c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]);
-        const M3b Tm = mb_mul(Wm, J);
-        const M3b cov2D = mb_mul(mb_mul(mb_t(Tm), mb_t(Vrk)), Tm);
-        const float a = cov2D.m[0][0] + 0.3f, b = cov2D.m[0][1], c = cov2D.m[1][1] + 0.3f;
+        const Cov2D cv = project_cov(V, p.focal, tx, ty, tz, c3);
+        const M3& Wm = cv.Wm;
+        const float a = cv.xx, b = cv.xy, c = cv.yy;
         const float denom = a * c - b * b;
         float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
         const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-#define TT(i, j) Tm.m[i][j]
-#define VV(i, j) Vrk.m[i][j]
+#define TT(i, j) cv.T.m[i][j]
+#define VV(i, j) cv.Vrk.m[i][j]
         if (denom2inv != 0.f) {
             dL_da = denom2inv * (-c * c * dcon_x + 2 * b * c * dcon_y + (denom - a * c) * dcon_w);
             dL_dc = denom2inv * (-a * a * dcon_w + 2 * a * b * dcon_y + (denom - a * c) * dcon_x);
@@ -215,23 +175,23 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(PreBwdParams p
         const float itz = 1.f / tz;
         const float tz2 = itz * itz;
         const float tz3 = tz2 * itz;
-        const float dL_dtx = x_grad_mul * -p.h_x * tz2 * dL_dJ02;
-        const float dL_dty = y_grad_mul * -p.h_y * tz2 * dL_dJ12;
-        const float dL_dtz = -p.h_x * tz2 * dL_dJ00 - p.h_y * tz2 * dL_dJ11 + (2 * p.h_x * tx) * tz3 * dL_dJ02 +
-                             (2 * p.h_y * ty) * tz3 * dL_dJ12;
+        const float dL_dtx = x_grad_mul * -p.focal.x * tz2 * dL_dJ02;
+        const float dL_dty = y_grad_mul * -p.focal.y * tz2 * dL_dJ12;
+        const float dL_dtz = -p.focal.x * tz2 * dL_dJ00 - p.focal.y * tz2 * dL_dJ11 + (2 * p.focal.x * tx) * tz3 * dL_dJ02 +
+                             (2 * p.focal.y * ty) * tz3 * dL_dJ12;
         g_mean[0] = V[0] * dL_dtx + V[1] * dL_dty + V[2] * dL_dtz;
         g_mean[1] = V[4] * dL_dtx + V[5] * dL_dty + V[6] * dL_dtz;
         g_mean[2] = V[8] * dL_dtx + V[9] * dL_dty + V[10] * dL_dtz;
 
         // ---- projection + depth path (backward.cu:346-403) ----
-        const float hw = Pm[3] * mx + Pm[7] * my + Pm[11] * mz + Pm[15];
-        const float m_w = 1.0f / (hw + 0.0000001f);
-        const float mul1 = (Pm[0] * mx + Pm[4] * my + Pm[8] * mz + Pm[12]) * m_w * m_w;
-        const float mul2 = (Pm[1] * mx + Pm[5] * my + Pm[9] * mz + Pm[13]) * m_w * m_w;
+        const float m_w = homog_inv_w(Pm, mx, my, mz);
+        const float2 hp = homog_xy(Pm, mx, my, mz);
+        const float mul1 = hp.x * m_w * m_w;
+        const float mul2 = hp.y * m_w * m_w;
         g_mean[0] += (Pm[0] * m_w - Pm[3] * mul1) * g_m2[0] + (Pm[1] * m_w - Pm[3] * mul2) * g_m2[1];
         g_mean[1] += (Pm[4] * m_w - Pm[7] * mul1) * g_m2[0] + (Pm[5] * m_w - Pm[7] * mul2) * g_m2[1];
         g_mean[2] += (Pm[8] * m_w - Pm[11] * mul1) * g_m2[0] + (Pm[9] * m_w - Pm[11] * mul2) * g_m2[1];
-        const float mul3 = V[2] * mx + V[6] * my + V[10] * mz + V[14];
+        const float mul3 = view_depth(V, mx, my, mz);
         g_mean[0] += (V[2] - V[3] * mul3) * g_depth;
         g_mean[1] += (V[6] - V[7] * mul3) * g_depth;
         g_mean[2] += (V[10] - V[11] * mul3) * g_depth;
@@ -250,26 +210,20 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(PreBwdParams p
         if (p.scales) {
             const float r = s_rot[4 * tid + 0], x = s_rot[4 * tid + 1];
             const float y = s_rot[4 * tid + 2], z = s_rot[4 * tid + 3];
-            const M3b R = mb_cols(
-                1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
-                2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x),
-                2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y));
-            const float s0 = p.scale_modifier * s_sc[3 * tid + 0];
-            const float s1 = p.scale_modifier * s_sc[3 * tid + 1];
-            const float s2 = p.scale_modifier * s_sc[3 * tid + 2];
-            M3b S = mb_cols(1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f);
-            S.m[0][0] = s0; S.m[1][1] = s1; S.m[2][2] = s2;
-            M3b M = mb_mul(S, R);
-            const M3b dSig = mb_cols(g_cov[0], 0.5f * g_cov[1], 0.5f * g_cov[2],
+            const M3 R = raw_quat_rotation(r, x, y, z);
+            const float3 sm = modified_scale(p.scale_modifier, s_sc + 3 * tid);
+            const float s0 = sm.x, s1 = sm.y, s2 = sm.z;
+            M3 M = scaled_rotation(sm, R);
+            const M3 dSig = m3_cols(g_cov[0], 0.5f * g_cov[1], 0.5f * g_cov[2],
                                      0.5f * g_cov[1], g_cov[3], 0.5f * g_cov[4],
                                      0.5f * g_cov[2], 0.5f * g_cov[4], g_cov[5]);
 #pragma unroll
             for (int cc = 0; cc < 3; cc++)
 #pragma unroll
                 for (int q = 0; q < 3; q++) M.m[cc][q] = 2.0f * M.m[cc][q];
-            const M3b dL_dM = mb_mul(M, dSig);
-            const M3b Rt = mb_t(R);
-            M3b D = mb_t(dL_dM);
+            const M3 dL_dM = m3_mul(M, dSig);
+            const M3 Rt = m3_t(R);
+            M3 D = m3_t(dL_dM);
             g_scale[0] = Rt.m[0][0] * D.m[0][0] + Rt.m[0][1] * D.m[0][1] + Rt.m[0][2] * D.m[0][2];
             g_scale[1] = Rt.m[1][0] * D.m[1][0] + Rt.m[1][1] * D.m[1][1] + Rt.m[1][2] * D.m[1][2];
             g_scale[2] = Rt.m[2][0] * D.m[2][0] + Rt.m[2][1] * D.m[2][1] + Rt.m[2][2] * D.m[2][2];
@@ -318,8 +272,7 @@ int launch_preprocess_backward(const AgRasterBackwardArgs& a, hipStream_t s)
 {
     PreBwdParams p;
     p.P = a.P;
-    p.h_y = a.H / (2.0f * a.tan_fovy);   // rasterizer_impl.cu:386-387
-    p.h_x = a.W / (2.0f * a.tan_fovx);
+    p.focal = focal_lengths(a.W, a.H, a.tan_fovx, a.tan_fovy);
     p.tan_fovx = a.tan_fovx; p.tan_fovy = a.tan_fovy; p.scale_modifier = a.scale_modifier;
     p.means3D = a.means3D; p.radii = a.radii; p.scales = a.scales; p.rotations = a.rotations;
     const char* gb = aligned_base(a.geom_buffer);
