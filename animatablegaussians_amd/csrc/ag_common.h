@@ -95,6 +95,15 @@ __device__ __forceinline__ float row_read(float v, int lane, int k)   // value o
     return __shfl(v, (lane & 48) + k, 64);
 }
 
+// Sum over the 64 lanes of a wavefront by xor-shuffle (32, 16, .. 1); every lane ends with the result.  (The matching maximum stays
+// written out where it is used, in ag_conv.hip and ag_styleunet_ops.hip: profiles/smplx_chain_ab.txt.)
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a workgroup-scope release fence, which on
 // gfx950 makes every wave wait for the acknowledgement of its outstanding global stores/atomics (vmcnt(0)) -- and, because
 // vmcnt retires in order, for any prefetch issued before them.  The blend kernels exchange data between waves through

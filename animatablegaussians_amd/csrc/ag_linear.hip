@@ -18,13 +18,6 @@ struct LinearLaunch {
     int32_t total_cols;
 };
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // 1 / sqrt(mean(x^2) + 1e-8) of one input row (PixelNorm, dual_styleunet.py:13-18), by the whole wave
 __device__ __forceinline__ float pixel_norm_factor(const float* __restrict__ x, int in, int lane)
 {

@@ -51,13 +51,6 @@ __global__ void __launch_bounds__(256) maxpool2x2_backward_kernel(float* __restr
 
 constexpr float kLpipsEps = 1e-10f;
 
-__device__ __forceinline__ float wave_sum64(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(256) lpips_level_forward_kernel(float* __restrict__ out, const float* __restrict__ f0,
                                                                  const float* __restrict__ f1, const float* __restrict__ lin, int C,
                                                                  int HW)
@@ -79,7 +72,7 @@ __global__ void __launch_bounds__(256) lpips_level_forward_kernel(float* __restr
         }
         acc += v;
     }
-    acc = wave_sum64(acc);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(out, ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) / (float)HW);

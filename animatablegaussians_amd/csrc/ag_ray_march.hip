@@ -19,7 +19,6 @@ namespace ag {
 namespace {
 
 using ray::bad_counts;
-using ray::butterfly_sum;
 
 constexpr int kThreads = 256;
 constexpr int kVertexTile = 1024;                  // vertices per LDS tile: 12 KiB
@@ -163,8 +162,8 @@ __global__ void __launch_bounds__(kThreads) ray_composite_kernel(const float* __
         if (valid && weights) weights[row + s] = w;
         float c0 = 0.f, c1 = 0.f, c2 = 0.f;
         if (valid && color) { c0 = color[3 * (row + s)]; c1 = color[3 * (row + s) + 1]; c2 = color[3 * (row + s) + 2]; }
-        const float t0 = butterfly_sum(w * c0), t1 = butterfly_sum(w * c1), t2 = butterfly_sum(w * c2);
-        const float ta = butterfly_sum(w), td = butterfly_sum(w * z);
+        const float t0 = wave_sum(w * c0), t1 = wave_sum(w * c1), t2 = wave_sum(w * c2);
+        const float ta = wave_sum(w), td = wave_sum(w * z);
         if (s0 == 0) { rgb0 = t0; rgb1 = t1; rgb2 = t2; acc = ta; depth = td; }
         else { rgb0 = rgb0 + t0; rgb1 = rgb1 + t1; rgb2 = rgb2 + t2; acc = acc + ta; depth = depth + td; }
     }

@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(kThreads) laplace_density_backward_kernel(cons
             const float dens = mlp::sdf_density(v, b, inv);
             term = g * (-dens / b + (((inv * 0.5f) * sgn) * ex) * av / (b * b));
         }
-        if (partials) sum = sum + (double)ray::butterfly_sum(term);      // uniform: partials is a kernel argument
+        if (partials) sum = sum + (double)wave_sum(term);      // uniform: partials is a kernel argument
     }
     if (partials && lane == 0) partials[wave] = sum;
 }

@@ -5,7 +5,8 @@
 //   dist      dist_s = z_{s+1} - z_s, dist_{S-1} = z_{S-1} - z_{S-2};
 //   product   P_l = f_0 * .. * f_l by six doubling steps o = 1, 2, 4, 8, 16, 32: every lane l >= o replaces p_l by p_{l-o} * p_l;
 //   T         T of lane l = carry * (l == 0 ? 1 : P_{l-1});  carry = 1 for the first chunk, carry * P_63 for the next one;
-//   sums      six butterfly steps o = 32, 16, 8, 4, 2, 1: v_l = v_l + v_{l xor o}, every lane ends with the chunk's sum.
+//   sums      six butterfly steps o = 32, 16, 8, 4, 2, 1: v_l = v_l + v_{l xor o}, every lane ends with the chunk's sum
+//             (wave_sum of ag_common.h).
 // Every lane of the wavefront must call these (cross-lane moves).  Units that include this are compiled WITHOUT fp contraction.
 #pragma once
 
@@ -16,13 +17,6 @@ namespace ag {
 namespace ray {
 
 constexpr int kRayThreads = 256;                   // four rays (wavefronts) per workgroup
-
-__device__ __forceinline__ float butterfly_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-    return v;
-}
 
 // z_s and dist_s of a valid sample s of the ray whose samples start at z_vals[row]
 __device__ __forceinline__ float sample_dist(const float* __restrict__ z_vals, long long row, int s, int S, float& z)

@@ -11,7 +11,10 @@
 //   skin_kernel    pose_offsets = features . posedirs (the 61 MB stream), v_posed, T = W . A, vertices
 //                  workgroup = 32 vertices x 8 slices of the 486 features; lanes along coordinates (256-B segments)
 // The backward of the kinematic chain is one launch (chain_backward_kernel); the backward of the vertex path (key points, skinning,
-// the two bases transposed) is the block of kernels after it, ahead of the host functions.
+// the two bases transposed) is the block of kernels after it, ahead of the host functions.  What a forward kernel and its backward must
+// agree on bit for bit is stated once: RodriguesHead, chain_forward (the chain itself), inverse4.
+#include <type_traits>
+
 #include "ag_common.h"
 #include "../../include/ag_smplx.h"
 
@@ -55,11 +58,9 @@ __global__ void __launch_bounds__(256) smplx_joints_kernel(float* __restrict__ o
         a1 = fmaf(w, vs[(size_t)(3 * v + 1) * src_stride], a1);
         a2 = fmaf(w, vs[(size_t)(3 * v + 2) * src_stride], a2);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        a0 += __shfl_xor(a0, o);
-        a1 += __shfl_xor(a1, o);
-        a2 += __shfl_xor(a2, o);
-    }
+    a0 = wave_sum(a0);
+    a1 = wave_sum(a1);
+    a2 = wave_sum(a2);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { s_part[wave][0] = a0; s_part[wave][1] = a1; s_part[wave][2] = a2; }
     __syncthreads();
@@ -73,14 +74,26 @@ struct Affine {   // [R | t], last row (0 0 0 1) implied
     float r[9], t[3];
 };
 
-// lbs.py:299-330.  The `+ 1e-8` goes into the norm only, the direction divides the untouched vector by it.
+// lbs.py:299-330, what rodrigues() and its backward both start from: R = I + s K + c1 K K with angle = |rv + 1e-8|, K = skew(rv / angle),
+// s = sin(angle), c1 = 1 - cos(angle).  The `+ 1e-8` goes into the norm only (e), the direction divides the untouched vector by it.
+struct RodriguesHead {
+    float e[3], angle, s, co, c1, K[9];
+    __device__ __forceinline__ explicit RodriguesHead(const float* rv)
+    {
+        for (int c = 0; c < 3; ++c) e[c] = rv[c] + 1e-8f;
+        angle = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+        const float rx = rv[0] / angle, ry = rv[1] / angle, rz = rv[2] / angle;
+        s = sinf(angle), co = cosf(angle), c1 = 1.f - co;
+        const float k[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
+        for (int i = 0; i < 9; ++i) K[i] = k[i];
+    }
+};
+
 __device__ __forceinline__ void rodrigues(const float* rv, float* R)
 {
-    const float ex = rv[0] + 1e-8f, ey = rv[1] + 1e-8f, ez = rv[2] + 1e-8f;
-    const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float rx = rv[0] / angle, ry = rv[1] / angle, rz = rv[2] / angle;
-    const float s = sinf(angle), c1 = 1.f - cosf(angle);
-    const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
+    const RodriguesHead h(rv);
+    const float s = h.s, c1 = h.c1;
+    const float* K = h.K;
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) {
             float kk = 0.f;
@@ -89,23 +102,35 @@ __device__ __forceinline__ void rodrigues(const float* rv, float* R)
         }
 }
 
-__global__ void __launch_bounds__(64) smplx_chain_kernel(float* __restrict__ A_out, float* __restrict__ A_skin,
-                                                        float* __restrict__ joints_out, float* __restrict__ pose_feature,
-                                                        const float* __restrict__ full_pose, const float* __restrict__ comps,
-                                                        const float* __restrict__ joint_template, const float* __restrict__ joint_dirs,
-                                                        const int* __restrict__ parents, const float* __restrict__ transl, int J, int NB)
-{
-    __shared__ Affine s_glob[kMaxJoints];
-    __shared__ float s_rest[kMaxJoints][3];
-    __shared__ int s_maxdepth;
-    const int b = blockIdx.x, j = threadIdx.x;
-    const bool on = j < J;
-    if (j == 0) s_maxdepth = 0;
-    __syncthreads();
+// The kinematic chain of one pose, by the one wave of its workgroup (lane = joint): what smplx_chain_kernel writes out and what
+// smplx_chain_backward_kernel recomputes, in one place so that the two agree bit for bit.
+struct alignas(16) ChainShared {    // in LDS.  16: an Affine is three 16-byte accesses
+    Affine glob[kMaxJoints];        // global transforms: G_j = G_parent [R_j | t_j]
+    float rest[kMaxJoints][3];      // rest joints
+    int par[kMaxJoints];
+    int maxdepth;
+};
 
+struct ChainLane {                  // what a joint's lane keeps in registers
+    Affine loc;                     // [R_j | t_j], t_j = rest_j - rest_parent
+    float rest[3];
+    int parent, depth;              // depth: steps to the root
+    int maxdepth;                   // of the whole tree (uniform)
+};
+
+// Fills `sh` (complete on return) and returns the lane's own values; lanes j >= J return rest = 0, parent = -1, depth = 0.  Every lane of
+// the workgroup must call it.
+__device__ __forceinline__ ChainLane chain_forward(ChainShared& sh, const float* __restrict__ full_pose, const float* __restrict__ comps,
+                                                   const float* __restrict__ joint_template, const float* __restrict__ joint_dirs,
+                                                   const int* __restrict__ parents, int b, int J, int NB)
+{
+    const int j = threadIdx.x;
+    const bool on = j < J;
     Affine loc;
     float rest[3] = {0.f, 0.f, 0.f};
     int parent = -1, depth = 0;
+    if (j == 0) sh.maxdepth = 0;
+    __syncthreads();
     if (on) {
         // lbs.py:208-212 with the regressor folded: J_regressor . (v_template + dirs . comps) = joint_template + joint_dirs . comps
         for (int c = 0; c < 3; ++c) {
@@ -113,45 +138,58 @@ __global__ void __launch_bounds__(64) smplx_chain_kernel(float* __restrict__ A_o
             float acc = 0.f;
             for (int l = 0; l < NB; ++l) acc = fmaf(d[l], comps[(size_t)b * NB + l], acc);
             rest[c] = joint_template[3 * j + c] + acc;
-            s_rest[j][c] = rest[c];
+            sh.rest[j][c] = rest[c];
         }
+        parent = parents[j];
+        sh.par[j] = parent;
     }
     __syncthreads();
     if (on) {
         rodrigues(full_pose + ((size_t)b * J + j) * 3, loc.r);
-        parent = parents[j];
-        for (int c = 0; c < 3; ++c) loc.t[c] = parent >= 0 ? rest[c] - s_rest[parent][c] : rest[c];
-        if (j >= 1) {
-            float* pf = pose_feature + (size_t)b * 9 * (J - 1) + 9 * (j - 1);
-            for (int k = 0; k < 9; ++k) pf[k] = loc.r[k] - ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f);
-        }
-        for (int p = parent; p >= 0; p = parents[p]) ++depth;
-        atomicMax(&s_maxdepth, depth);
-        if (depth == 0) s_glob[j] = loc;
+        for (int c = 0; c < 3; ++c) loc.t[c] = parent >= 0 ? rest[c] - sh.rest[parent][c] : rest[c];
+        for (int p = parent; p >= 0; p = sh.par[p]) ++depth;
+        atomicMax(&sh.maxdepth, depth);
+        if (depth == 0) sh.glob[j] = loc;
     }
     __syncthreads();
-    const int maxdepth = s_maxdepth;
+    const int maxdepth = sh.maxdepth;
     // lbs.py:389-395: transform_chain[i] = transform_chain[parents[i]] @ transforms_mat[i], one tree level per step
     for (int d = 1; d <= maxdepth; ++d) {
         if (on && depth == d) {
-            const Affine& P = s_glob[parent];
+            const Affine& P = sh.glob[parent];
             Affine g;
             for (int r = 0; r < 3; ++r) {
                 for (int c = 0; c < 3; ++c)
                     g.r[3 * r + c] = fmaf(P.r[3 * r + 2], loc.r[6 + c], fmaf(P.r[3 * r + 1], loc.r[3 + c], P.r[3 * r] * loc.r[c]));
                 g.t[r] = fmaf(P.r[3 * r + 2], loc.t[2], fmaf(P.r[3 * r + 1], loc.t[1], P.r[3 * r] * loc.t[0])) + P.t[r];
             }
-            s_glob[j] = g;
+            sh.glob[j] = g;
         }
         __syncthreads();
     }
-    if (!on) return;
-    const Affine g = s_glob[j];
+    return {loc, {rest[0], rest[1], rest[2]}, parent, depth, maxdepth};
+}
+
+__global__ void __launch_bounds__(64) smplx_chain_kernel(float* __restrict__ A_out, float* __restrict__ A_skin,
+                                                        float* __restrict__ joints_out, float* __restrict__ pose_feature,
+                                                        const float* __restrict__ full_pose, const float* __restrict__ comps,
+                                                        const float* __restrict__ joint_template, const float* __restrict__ joint_dirs,
+                                                        const int* __restrict__ parents, const float* __restrict__ transl, int J, int NB)
+{
+    __shared__ ChainShared sh;
+    const int b = blockIdx.x, j = threadIdx.x;
+    const ChainLane me = chain_forward(sh, full_pose, comps, joint_template, joint_dirs, parents, b, J, NB);
+    if (j >= J) return;
+    if (j >= 1) {       // lbs.py:221
+        float* pf = pose_feature + (size_t)b * 9 * (J - 1) + 9 * (j - 1);
+        for (int k = 0; k < 9; ++k) pf[k] = me.loc.r[k] - ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f);
+    }
+    const Affine g = sh.glob[j];
     float* Aj = A_out + ((size_t)b * J + j) * 16;
     float* As = A_skin + ((size_t)b * J + j) * 12;
     for (int r = 0; r < 3; ++r) {
         // lbs.py:402-403: rel = T - pad(T @ [J; 0]) -> translation column minus R . J_rest
-        const float rj = fmaf(g.r[3 * r + 2], rest[2], fmaf(g.r[3 * r + 1], rest[1], g.r[3 * r] * rest[0]));
+        const float rj = fmaf(g.r[3 * r + 2], me.rest[2], fmaf(g.r[3 * r + 1], me.rest[1], g.r[3 * r] * me.rest[0]));
         const float tr = transl ? transl[3 * b + r] : 0.f;
         for (int c = 0; c < 3; ++c) Aj[4 * r + c] = As[4 * r + c] = g.r[3 * r + c];
         As[4 * r + 3] = g.t[r] - rj;                     // what the skinning uses (lbs.py:241)
@@ -251,229 +289,6 @@ __global__ void __launch_bounds__(64) smplx_keypoints_kernel(float* __restrict__
     out[((size_t)b * K + k) * 3 + c] = acc;
 }
 
-__global__ void __launch_bounds__(64) mat4_mul_inverse_kernel(float* __restrict__ out, const float* __restrict__ a,
-                                                             const float* __restrict__ bm, int n, int b_batch)
-{
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    float m[16], inv[16];
-    for (int k = 0; k < 16; ++k) m[k] = bm[(size_t)(i % b_batch) * 16 + k];
-    // general 4x4 inverse through the 2x2 minors of the top and bottom row pairs (adjugate / determinant)
-    const float s0 = m[0] * m[5] - m[4] * m[1], s1 = m[0] * m[6] - m[4] * m[2], s2 = m[0] * m[7] - m[4] * m[3];
-    const float s3 = m[1] * m[6] - m[5] * m[2], s4 = m[1] * m[7] - m[5] * m[3], s5 = m[2] * m[7] - m[6] * m[3];
-    const float c5 = m[10] * m[15] - m[14] * m[11], c4 = m[9] * m[15] - m[13] * m[11], c3 = m[9] * m[14] - m[13] * m[10];
-    const float c2 = m[8] * m[15] - m[12] * m[11], c1 = m[8] * m[14] - m[12] * m[10], c0 = m[8] * m[13] - m[12] * m[9];
-    const float det = s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
-    const float id = 1.f / det;
-    inv[0] = (m[5] * c5 - m[6] * c4 + m[7] * c3) * id;
-    inv[1] = (-m[1] * c5 + m[2] * c4 - m[3] * c3) * id;
-    inv[2] = (m[13] * s5 - m[14] * s4 + m[15] * s3) * id;
-    inv[3] = (-m[9] * s5 + m[10] * s4 - m[11] * s3) * id;
-    inv[4] = (-m[4] * c5 + m[6] * c2 - m[7] * c1) * id;
-    inv[5] = (m[0] * c5 - m[2] * c2 + m[3] * c1) * id;
-    inv[6] = (-m[12] * s5 + m[14] * s2 - m[15] * s1) * id;
-    inv[7] = (m[8] * s5 - m[10] * s2 + m[11] * s1) * id;
-    inv[8] = (m[4] * c4 - m[5] * c2 + m[7] * c0) * id;
-    inv[9] = (-m[0] * c4 + m[1] * c2 - m[3] * c0) * id;
-    inv[10] = (m[12] * s4 - m[13] * s2 + m[15] * s0) * id;
-    inv[11] = (-m[8] * s4 + m[9] * s2 - m[11] * s0) * id;
-    inv[12] = (-m[4] * c3 + m[5] * c1 - m[6] * c0) * id;
-    inv[13] = (m[0] * c3 - m[1] * c1 + m[2] * c0) * id;
-    inv[14] = (-m[12] * s3 + m[13] * s1 - m[14] * s0) * id;
-    inv[15] = (m[8] * s3 - m[9] * s1 + m[10] * s0) * id;
-    const float* ai = a + (size_t)i * 16;
-    float* oi = out + (size_t)i * 16;
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) {
-            float acc = 0.f;
-            for (int k = 0; k < 4; ++k) acc = fmaf(ai[4 * r + k], inv[4 * k + c], acc);
-            oi[4 * r + c] = acc;
-        }
-}
-
-// Backward of rodrigues(): R = I + sin(t) K + (1 - cos(t)) K K with t = |rv + 1e-8|, K = skew(rv / t).  dR [9] -> drv [3].
-// The eps keeps the zero pose's gradient finite, as in the reference (its torch autograd of the same expression).
-__device__ __forceinline__ void rodrigues_backward(const float* rv, const float* dR, float* drv)
-{
-    const float e[3] = {rv[0] + 1e-8f, rv[1] + 1e-8f, rv[2] + 1e-8f};
-    const float angle = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
-    const float rx = rv[0] / angle, ry = rv[1] / angle, rz = rv[2] / angle;
-    const float s = sinf(angle), co = cosf(angle), c1 = 1.f - co;
-    const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
-    float ds = 0.f, dc1 = 0.f, dK[9];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            float kk = 0.f, t = 0.f;
-            for (int k = 0; k < 3; ++k) {
-                kk = fmaf(K[3 * r + k], K[3 * k + c], kk);
-                t += dR[3 * r + k] * K[3 * c + k] + K[3 * k + r] * dR[3 * k + c];     // (dR K^T + K^T dR)[r][c]
-            }
-            ds += dR[3 * r + c] * K[3 * r + c];
-            dc1 += dR[3 * r + c] * kk;
-            dK[3 * r + c] = s * dR[3 * r + c] + c1 * t;
-        }
-    const float da[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
-    // axis = rv / angle;  angle = |e|
-    const float dangle = ds * co + dc1 * s - (da[0] * rv[0] + da[1] * rv[1] + da[2] * rv[2]) / (angle * angle);
-    for (int c = 0; c < 3; ++c) drv[c] = da[c] / angle + dangle * e[c] / angle;
-}
-
-// Reverse of smplx_chain_kernel, one wave per pose: recomputes the rest joints, the local transforms and the global chain, then walks
-// the tree levels from the deepest to the root.  A parent gathers its children's contributions in ascending joint order, so the
-// result does not depend on scheduling.  Inputs dA [B][J][4][4] (row 3 unused) and djoints [B][J][3], either may be NULL.
-// Outputs: dpose [B][J][3]; dtransl [B][3] (NULL: skipped); dcomps [B][NB] through the folded joint_dirs (NULL: skipped).
-// EXT (ag_smplx_backward_full) adds what the vertex path hands over, each NULL or present: dAs [B][J][12] on the un-translated matrices
-// the skinning read (joins dA everywhere except in dtransl), dfeat [B][J-1][9] on the local rotations R[1:] (joins dR ahead of the
-// Rodrigues backward), dtr_add [B][3] and dcomps_add [B][NB] (added to the two outputs last).  EXT = false is the kernel as it was.
-template <bool EXT>
-__global__ void __launch_bounds__(64) smplx_chain_backward_kernel(float* __restrict__ dpose, float* __restrict__ dtransl,
-                                                                 float* __restrict__ dcomps, const float* __restrict__ dA,
-                                                                 const float* __restrict__ djoints, const float* __restrict__ full_pose,
-                                                                 const float* __restrict__ comps, const float* __restrict__ joint_template,
-                                                                 const float* __restrict__ joint_dirs, const int* __restrict__ parents,
-                                                                 int J, int NB, const float* __restrict__ dAs, const float* __restrict__ dfeat,
-                                                                 const float* __restrict__ dtr_add, const float* __restrict__ dcomps_add)
-{
-    __shared__ Affine s_glob[kMaxJoints];
-    __shared__ float s_rest[kMaxJoints][3];
-    __shared__ float s_cr[kMaxJoints][9];     // a joint's contribution to its parent's dL/d(global rotation)
-    __shared__ float s_ct[kMaxJoints][3];     // ... to its parent's dL/d(global translation)
-    __shared__ float s_dt[kMaxJoints][3];     // dL/d(local translation) = dL/d(rest_j - rest_parent)
-    __shared__ float s_drest[kMaxJoints][3];
-    __shared__ int s_par[kMaxJoints];
-    __shared__ int s_maxdepth;
-    const int b = blockIdx.x, j = threadIdx.x;
-    const bool on = j < J;
-    if (j == 0) s_maxdepth = 0;
-    __syncthreads();
-
-    // ---- forward recompute (smplx_chain_kernel) ----
-    Affine loc;
-    float rest[3] = {0.f, 0.f, 0.f};
-    int parent = -1, depth = 0;
-    if (on) {
-        for (int c = 0; c < 3; ++c) {
-            const float* d = joint_dirs + (size_t)(3 * j + c) * NB;
-            float acc = 0.f;
-            for (int l = 0; l < NB; ++l) acc = fmaf(d[l], comps[(size_t)b * NB + l], acc);
-            rest[c] = joint_template[3 * j + c] + acc;
-            s_rest[j][c] = rest[c];
-        }
-        parent = parents[j];
-        s_par[j] = parent;
-    }
-    __syncthreads();
-    if (on) {
-        rodrigues(full_pose + ((size_t)b * J + j) * 3, loc.r);
-        for (int c = 0; c < 3; ++c) loc.t[c] = parent >= 0 ? rest[c] - s_rest[parent][c] : rest[c];
-        for (int p = parent; p >= 0; p = s_par[p]) ++depth;
-        atomicMax(&s_maxdepth, depth);
-        if (depth == 0) s_glob[j] = loc;
-    }
-    __syncthreads();
-    const int maxdepth = s_maxdepth;
-    for (int d = 1; d <= maxdepth; ++d) {
-        if (on && depth == d) {
-            const Affine& P = s_glob[parent];
-            Affine g;
-            for (int r = 0; r < 3; ++r) {
-                for (int c = 0; c < 3; ++c)
-                    g.r[3 * r + c] = fmaf(P.r[3 * r + 2], loc.r[6 + c], fmaf(P.r[3 * r + 1], loc.r[3 + c], P.r[3 * r] * loc.r[c]));
-                g.t[r] = fmaf(P.r[3 * r + 2], loc.t[2], fmaf(P.r[3 * r + 1], loc.t[1], P.r[3 * r] * loc.t[0])) + P.t[r];
-            }
-            s_glob[j] = g;
-        }
-        __syncthreads();
-    }
-
-    // ---- direct gradients: A_j[:3, :3] = Gr_j;  A_j[:3, 3] = Gt_j - Gr_j rest_j (+ transl);  joints_j = Gt_j (+ transl) ----
-    float dGr[9], dGt[3], drest[3] = {0.f, 0.f, 0.f};
-    if (on) {
-        const float* a = dA ? dA + ((size_t)b * J + j) * 16 : nullptr;
-        const float* dj = djoints ? djoints + ((size_t)b * J + j) * 3 : nullptr;
-        const Affine& g = s_glob[j];
-        const float* as = EXT && dAs ? dAs + ((size_t)b * J + j) * 12 : nullptr;
-        float dtr[3];     // the part of dGt that transl sees: dAs belongs to the matrices before transl was added
-        for (int r = 0; r < 3; ++r) {
-            float dcol = a ? a[4 * r + 3] : 0.f;
-            dtr[r] = dcol + (dj ? dj[r] : 0.f);
-            if (EXT && as) dcol += as[4 * r + 3];
-            dGt[r] = dcol + (dj ? dj[r] : 0.f);
-            for (int c = 0; c < 3; ++c) {
-                float da = a ? a[4 * r + c] : 0.f;
-                if (EXT && as) da += as[4 * r + c];
-                dGr[3 * r + c] = da - dcol * rest[c];
-                drest[c] -= g.r[3 * r + c] * dcol;
-            }
-        }
-        for (int r = 0; r < 3; ++r) s_ct[j][r] = EXT ? dtr[r] : dGt[r];      // read by the dtransl sum only; the level loop rewrites it
-    }
-    __syncthreads();
-    if (dtransl && j < 3) {           // body_models.py:1272-1275: transl is added to every A_j[:3, 3] and every joint
-        float acc = 0.f;
-        for (int k = 0; k < J; ++k) acc += s_ct[k][j];
-        if (EXT && dtr_add) acc += dtr_add[3 * b + j];
-        dtransl[3 * b + j] = acc;
-    }
-    __syncthreads();
-
-    // ---- the chain in reverse, one tree level per step ----
-    for (int d = maxdepth; d >= 0; --d) {
-        if (on && depth == d) {
-            // Gr_j = Gr_p R_j,  Gt_j = Gr_p t_j + Gt_p   (root: Gr_0 = R_0, Gt_0 = t_0)
-            float dR[9], dt[3];
-            if (parent >= 0) {
-                const Affine& P = s_glob[parent];
-                for (int k = 0; k < 3; ++k) {
-                    for (int c = 0; c < 3; ++c)
-                        dR[3 * k + c] = P.r[k] * dGr[c] + P.r[3 + k] * dGr[3 + c] + P.r[6 + k] * dGr[6 + c];
-                    dt[k] = P.r[k] * dGt[0] + P.r[3 + k] * dGt[1] + P.r[6 + k] * dGt[2];
-                }
-                for (int r = 0; r < 3; ++r) {
-                    for (int k = 0; k < 3; ++k)
-                        s_cr[j][3 * r + k] = dGr[3 * r] * loc.r[3 * k] + dGr[3 * r + 1] * loc.r[3 * k + 1] + dGr[3 * r + 2] * loc.r[3 * k + 2] +
-                                             dGt[r] * loc.t[k];
-                    s_ct[j][r] = dGt[r];
-                }
-            } else {
-                for (int k = 0; k < 9; ++k) dR[k] = dGr[k];
-                for (int k = 0; k < 3; ++k) dt[k] = dGt[k];
-            }
-            for (int k = 0; k < 3; ++k) s_dt[j][k] = dt[k];
-            if (EXT && dfeat && j >= 1)       // lbs.py:221: pose_feature = R[1:] - I
-                for (int k = 0; k < 9; ++k) dR[k] += dfeat[(size_t)b * 9 * (J - 1) + 9 * (j - 1) + k];
-            rodrigues_backward(full_pose + ((size_t)b * J + j) * 3, dR, dpose + ((size_t)b * J + j) * 3);
-        }
-        __syncthreads();
-        if (on && depth == d - 1) {
-            for (int c = j + 1; c < J; ++c)
-                if (s_par[c] == j) {
-                    for (int k = 0; k < 9; ++k) dGr[k] += s_cr[c][k];
-                    for (int k = 0; k < 3; ++k) dGt[k] += s_ct[c][k];
-                }
-        }
-        __syncthreads();
-    }
-
-    // ---- rest joints: t_j = rest_j - rest_parent;  rest_j = joint_template_j + joint_dirs_j . comps ----
-    if (on) {
-        for (int k = 0; k < 3; ++k) drest[k] += s_dt[j][k];
-        for (int c = j + 1; c < J; ++c)
-            if (s_par[c] == j)
-                for (int k = 0; k < 3; ++k) drest[k] -= s_dt[c][k];
-        for (int k = 0; k < 3; ++k) s_drest[j][k] = drest[k];
-    }
-    __syncthreads();
-    if (dcomps)
-        for (int l = j; l < NB; l += 64) {
-            float acc = 0.f;
-            for (int k = 0; k < J; ++k)
-                for (int c = 0; c < 3; ++c) acc = fmaf(s_drest[k][c], joint_dirs[(size_t)(3 * k + c) * NB + l], acc);
-            if (EXT && dcomps_add) acc += dcomps_add[(size_t)b * NB + l];
-            dcomps[(size_t)b * NB + l] = acc;
-        }
-}
-
 // general 4x4 inverse through the 2x2 minors of the top and bottom row pairs (adjugate / determinant)
 __device__ __forceinline__ void inverse4(const float* m, float* inv)
 {
@@ -499,6 +314,161 @@ __device__ __forceinline__ void inverse4(const float* m, float* inv)
     inv[13] = (m[0] * c3 - m[1] * c1 + m[2] * c0) * id;
     inv[14] = (-m[12] * s3 + m[13] * s1 - m[14] * s0) * id;
     inv[15] = (m[8] * s3 - m[9] * s1 + m[10] * s0) * id;
+}
+
+__global__ void __launch_bounds__(64) mat4_mul_inverse_kernel(float* __restrict__ out, const float* __restrict__ a,
+                                                             const float* __restrict__ bm, int n, int b_batch)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    float inv[16];
+    inverse4(bm + (size_t)(i % b_batch) * 16, inv);
+    const float* ai = a + (size_t)i * 16;
+    float* oi = out + (size_t)i * 16;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            float acc = 0.f;
+            for (int k = 0; k < 4; ++k) acc = fmaf(ai[4 * r + k], inv[4 * k + c], acc);
+            oi[4 * r + c] = acc;
+        }
+}
+
+// Backward of rodrigues().  dR [9] -> drv [3].  The eps keeps the zero pose's gradient finite, as in the reference (its torch autograd of
+// the same expression).
+__device__ __forceinline__ void rodrigues_backward(const float* rv, const float* dR, float* drv)
+{
+    const RodriguesHead h(rv);
+    const float angle = h.angle, s = h.s, co = h.co, c1 = h.c1;
+    const float *e = h.e, *K = h.K;
+    float ds = 0.f, dc1 = 0.f, dK[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            float kk = 0.f, t = 0.f;
+            for (int k = 0; k < 3; ++k) {
+                kk = fmaf(K[3 * r + k], K[3 * k + c], kk);
+                t += dR[3 * r + k] * K[3 * c + k] + K[3 * k + r] * dR[3 * k + c];     // (dR K^T + K^T dR)[r][c]
+            }
+            ds += dR[3 * r + c] * K[3 * r + c];
+            dc1 += dR[3 * r + c] * kk;
+            dK[3 * r + c] = s * dR[3 * r + c] + c1 * t;
+        }
+    const float da[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
+    // axis = rv / angle;  angle = |e|
+    const float dangle = ds * co + dc1 * s - (da[0] * rv[0] + da[1] * rv[1] + da[2] * rv[2]) / (angle * angle);
+    for (int c = 0; c < 3; ++c) drv[c] = da[c] / angle + dangle * e[c] / angle;
+}
+
+// Reverse of smplx_chain_kernel, one wave per pose: recomputes the rest joints, the local transforms and the global chain (chain_forward),
+// then walks the tree levels from the deepest to the root.  A parent gathers its children's contributions in ascending joint order, so the
+// result does not depend on scheduling.  Inputs dA [B][J][4][4] (row 3 unused) and djoints [B][J][3], either may be NULL.
+// Outputs: dpose [B][J][3]; dtransl [B][3] (NULL: skipped); dcomps [B][NB] through the folded joint_dirs (NULL: skipped).
+// EXT (ag_smplx_backward_full) adds what the vertex path hands over, each NULL or present: dAs [B][J][12] on the un-translated matrices
+// the skinning read (joins dA everywhere except in dtransl), dfeat [B][J-1][9] on the local rotations R[1:] (joins dR ahead of the
+// Rodrigues backward), dtr_add [B][3] and dcomps_add [B][NB] (added to the two outputs last).  EXT = false is the kernel as it was.
+template <bool EXT>
+__global__ void __launch_bounds__(64) smplx_chain_backward_kernel(float* __restrict__ dpose, float* __restrict__ dtransl,
+                                                                 float* __restrict__ dcomps, const float* __restrict__ dA,
+                                                                 const float* __restrict__ djoints, const float* __restrict__ full_pose,
+                                                                 const float* __restrict__ comps, const float* __restrict__ joint_template,
+                                                                 const float* __restrict__ joint_dirs, const int* __restrict__ parents,
+                                                                 int J, int NB, const float* __restrict__ dAs, const float* __restrict__ dfeat,
+                                                                 const float* __restrict__ dtr_add, const float* __restrict__ dcomps_add)
+{
+    __shared__ ChainShared sh;
+    __shared__ float s_cr[kMaxJoints][9];     // a joint's contribution to its parent's dL/d(global rotation)
+    __shared__ float s_ct[kMaxJoints][3];     // ... to its parent's dL/d(global translation)
+    __shared__ float s_dt[kMaxJoints][3];     // dL/d(local translation) = dL/d(rest_j - rest_parent)
+    __shared__ float s_drest[kMaxJoints][3];
+    const int b = blockIdx.x, j = threadIdx.x;
+    const bool on = j < J;
+    const ChainLane me = chain_forward(sh, full_pose, comps, joint_template, joint_dirs, parents, b, J, NB);
+
+    // ---- direct gradients: A_j[:3, :3] = Gr_j;  A_j[:3, 3] = Gt_j - Gr_j rest_j (+ transl);  joints_j = Gt_j (+ transl) ----
+    float dGr[9], dGt[3], drest[3] = {0.f, 0.f, 0.f};
+    if (on) {
+        const float* a = dA ? dA + ((size_t)b * J + j) * 16 : nullptr;
+        const float* dj = djoints ? djoints + ((size_t)b * J + j) * 3 : nullptr;
+        const Affine& g = sh.glob[j];
+        const float* as = EXT && dAs ? dAs + ((size_t)b * J + j) * 12 : nullptr;
+        float dtr[3];     // the part of dGt that transl sees: dAs belongs to the matrices before transl was added
+        for (int r = 0; r < 3; ++r) {
+            float dcol = a ? a[4 * r + 3] : 0.f;
+            dtr[r] = dcol + (dj ? dj[r] : 0.f);
+            if (EXT && as) dcol += as[4 * r + 3];
+            dGt[r] = dcol + (dj ? dj[r] : 0.f);
+            for (int c = 0; c < 3; ++c) {
+                float da = a ? a[4 * r + c] : 0.f;
+                if (EXT && as) da += as[4 * r + c];
+                dGr[3 * r + c] = da - dcol * me.rest[c];
+                drest[c] -= g.r[3 * r + c] * dcol;
+            }
+        }
+        for (int r = 0; r < 3; ++r) s_ct[j][r] = EXT ? dtr[r] : dGt[r];      // read by the dtransl sum only; the level loop rewrites it
+    }
+    __syncthreads();
+    if (dtransl && j < 3) {           // body_models.py:1272-1275: transl is added to every A_j[:3, 3] and every joint
+        float acc = 0.f;
+        for (int k = 0; k < J; ++k) acc += s_ct[k][j];
+        if (EXT && dtr_add) acc += dtr_add[3 * b + j];
+        dtransl[3 * b + j] = acc;
+    }
+    __syncthreads();
+
+    // ---- the chain in reverse, one tree level per step ----
+    for (int d = me.maxdepth; d >= 0; --d) {
+        if (on && me.depth == d) {
+            // Gr_j = Gr_p R_j,  Gt_j = Gr_p t_j + Gt_p   (root: Gr_0 = R_0, Gt_0 = t_0)
+            float dR[9], dt[3];
+            if (me.parent >= 0) {
+                const Affine& P = sh.glob[me.parent];
+                for (int k = 0; k < 3; ++k) {
+                    for (int c = 0; c < 3; ++c)
+                        dR[3 * k + c] = P.r[k] * dGr[c] + P.r[3 + k] * dGr[3 + c] + P.r[6 + k] * dGr[6 + c];
+                    dt[k] = P.r[k] * dGt[0] + P.r[3 + k] * dGt[1] + P.r[6 + k] * dGt[2];
+                }
+                for (int r = 0; r < 3; ++r) {
+                    for (int k = 0; k < 3; ++k)
+                        s_cr[j][3 * r + k] = dGr[3 * r] * me.loc.r[3 * k] + dGr[3 * r + 1] * me.loc.r[3 * k + 1] +
+                                             dGr[3 * r + 2] * me.loc.r[3 * k + 2] + dGt[r] * me.loc.t[k];
+                    s_ct[j][r] = dGt[r];
+                }
+            } else {
+                for (int k = 0; k < 9; ++k) dR[k] = dGr[k];
+                for (int k = 0; k < 3; ++k) dt[k] = dGt[k];
+            }
+            for (int k = 0; k < 3; ++k) s_dt[j][k] = dt[k];
+            if (EXT && dfeat && j >= 1)       // lbs.py:221: pose_feature = R[1:] - I
+                for (int k = 0; k < 9; ++k) dR[k] += dfeat[(size_t)b * 9 * (J - 1) + 9 * (j - 1) + k];
+            rodrigues_backward(full_pose + ((size_t)b * J + j) * 3, dR, dpose + ((size_t)b * J + j) * 3);
+        }
+        __syncthreads();
+        if (on && me.depth == d - 1) {
+            for (int c = j + 1; c < J; ++c)
+                if (sh.par[c] == j) {
+                    for (int k = 0; k < 9; ++k) dGr[k] += s_cr[c][k];
+                    for (int k = 0; k < 3; ++k) dGt[k] += s_ct[c][k];
+                }
+        }
+        __syncthreads();
+    }
+
+    // ---- rest joints: t_j = rest_j - rest_parent;  rest_j = joint_template_j + joint_dirs_j . comps ----
+    if (on) {
+        for (int k = 0; k < 3; ++k) drest[k] += s_dt[j][k];
+        for (int c = j + 1; c < J; ++c)
+            if (sh.par[c] == j)
+                for (int k = 0; k < 3; ++k) drest[k] -= s_dt[c][k];
+        for (int k = 0; k < 3; ++k) s_drest[j][k] = drest[k];
+    }
+    __syncthreads();
+    if (dcomps)
+        for (int l = j; l < NB; l += 64) {
+            float acc = 0.f;
+            for (int k = 0; k < J; ++k)
+                for (int c = 0; c < 3; ++c) acc = fmaf(s_drest[k][c], joint_dirs[(size_t)(3 * k + c) * NB + l], acc);
+            if (EXT && dcomps_add) acc += dcomps_add[(size_t)b * NB + l];
+            dcomps[(size_t)b * NB + l] = acc;
+        }
 }
 
 // Backward of out[i] = a[i] X,  X = inverse(b[i % b_batch]):  da[i] = dout[i] X^T;  db[k] = -X^T (sum_{i % b_batch == k} a[i]^T dout[i]) X^T.
@@ -724,8 +694,7 @@ __global__ void __launch_bounds__(kPdThreads) smplx_posedirs_t_kernel(float* __r
         for (int b = 0; b < NBATCH; ++b) acc[b] = fmaf(d, dvp[(size_t)b * n_coord + c], acc[b]);
     }
     for (int b = 0; b < NBATCH; ++b) {
-        float a = acc[b];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        const float a = wave_sum(acc[b]);
         if ((tid & 63) == 0) s_part[b][tid >> 6] = a;
     }
     __syncthreads();
@@ -748,8 +717,7 @@ __global__ void __launch_bounds__(kSdCoords) smplx_dirs_t_kernel(float* __restri
     const float xv = live ? x[(size_t)b * n_coord + c] : 0.f;
     const float* row = dirs + (size_t)(live ? c : 0) * NB;
     for (int k = 0; k < NB; ++k) {
-        float a = live ? row[k] * xv : 0.f;
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        const float a = wave_sum(live ? row[k] * xv : 0.f);
         if ((tid & 63) == 0) s_sum[(tid >> 6) * NB + k] = a;
     }
     __syncthreads();
@@ -768,6 +736,31 @@ static bool folded_ok(const AgSmplxModel* m)
     return m->joint_template && (m->NB == 0 || m->joint_dirs);
 }
 
+// What the entry points of the forward and of its backward check first; `fn` names the caller in the message.  True: the call is over and
+// *rc is its result (a refusal, or AG_OK for B = 0: nothing to do).
+static bool call_is_over(const char* fn, const AgSmplxModel* m, int32_t B, bool folded, int* rc)
+{
+    *rc = AG_ERR_INVALID_ARGUMENT;
+    if (!model_ok(m)) set_error("%s: bad model (need 0 < J <= 64, non-null arrays)", fn);
+    else if (folded && !folded_ok(m)) set_error("%s: joint_template / joint_dirs missing -- run ag_smplx_prepare once per model", fn);
+    else if (B < 0) set_error("%s: B < 0", fn);
+    else { *rc = AG_OK; return B == 0; }
+    return true;
+}
+
+// f(first pose, std::integral_constant<int, NBATCH>) for every run of up to four poses of B: the kernels that read a basis once for NBATCH poses
+template <class F>
+static void for_pose_runs(int B, F f)
+{
+    for (int b0 = 0; b0 < B; b0 += 4)
+        switch (B - b0) {
+            case 1: f(b0, std::integral_constant<int, 1>()); break;
+            case 2: f(b0, std::integral_constant<int, 2>()); break;
+            case 3: f(b0, std::integral_constant<int, 3>()); break;
+            default: f(b0, std::integral_constant<int, 4>()); break;
+        }
+}
+
 template <int NBATCH>
 static void launch_skin(const AgSmplxModel* m, float* vertices, const float* feat, const float* v_shaped, const float* A,
                         const float* transl, float* v_posed, hipStream_t s)
@@ -778,6 +771,24 @@ static void launch_skin(const AgSmplxModel* m, float* vertices, const float* fea
     const int grid = (m->V + kSkinVerts - 1) / kSkinVerts;
     hipLaunchKernelGGL(smplx_skin_kernel<NBATCH>, dim3(grid), dim3(kSkinThreads), lds, s, vertices, m->posedirs, feat, v_shaped, A,
                        m->lbs_weights, transl, v_posed, m->V, m->J, P);
+}
+
+// ag_smplx_backward (EXT = false, the four handed-over gradients NULL) and ag_smplx_backward_full (EXT = true); `fn` names the caller in the
+// messages.
+template <bool EXT>
+static int chain_backward_impl(const char* fn, const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose,
+                               const float* dL_dA, const float* dL_djoints, const float* dL_dA_skin, const float* dL_dfeat,
+                               const float* dL_dtransl_add, const float* dL_dshape_components_add, float* dL_dfull_pose, float* dL_dtransl,
+                               float* dL_dshape_components, void* stream)
+{
+    int rc;
+    if (call_is_over(fn, m, B, true, &rc)) return rc;
+    if (!full_pose || !dL_dfull_pose || (m->NB > 0 && !shape_components)) { set_error("%s: null pointer", fn); return AG_ERR_INVALID_ARGUMENT; }
+    hipLaunchKernelGGL(smplx_chain_backward_kernel<EXT>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), dL_dfull_pose, dL_dtransl,
+                       m->NB > 0 ? dL_dshape_components : nullptr, dL_dA, dL_djoints, full_pose, shape_components, m->joint_template,
+                       m->joint_dirs, m->parents, m->J, m->NB, dL_dA_skin, dL_dfeat, dL_dtransl_add,
+                       m->NB > 0 ? dL_dshape_components_add : nullptr);
+    return check_hip(hipGetLastError(), "smplx_chain_backward_kernel");
 }
 
 }  // namespace ag
@@ -797,10 +808,8 @@ size_t ag_smplx_workspace_floats(const AgSmplxModel* m, int32_t B)
 static int smplx_forward_impl(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* transl,
                               float* vertices, float* joints, float* A, float* workspace, size_t workspace_floats, float* saved, void* stream)
 {
-    if (!model_ok(m)) { set_error("smplx: bad model (need 0 < J <= 64, non-null arrays)"); return AG_ERR_INVALID_ARGUMENT; }
-    if (!folded_ok(m)) { set_error("smplx: joint_template / joint_dirs missing -- run ag_smplx_prepare once per model"); return AG_ERR_INVALID_ARGUMENT; }
-    if (B < 0) { set_error("smplx: B < 0"); return AG_ERR_INVALID_ARGUMENT; }
-    if (B == 0) return AG_OK;
+    int rc;
+    if (call_is_over("smplx", m, B, true, &rc)) return rc;
     if (!full_pose || !vertices || !joints || !A || !workspace || (m->NB > 0 && !shape_components)) {
         set_error("smplx: null pointer");
         return AG_ERR_INVALID_ARGUMENT;
@@ -816,21 +825,11 @@ static int smplx_forward_impl(const AgSmplxModel* m, int32_t B, const float* sha
                        m->v_template, m->shapedirs, shape_components, n_coord, m->NB);
     hipLaunchKernelGGL(smplx_chain_kernel, dim3(B), dim3(64), 0, s, A, A_skin, joints, feat, full_pose, shape_components, m->joint_template,
                        m->joint_dirs, m->parents, transl, m->J, m->NB);
-    for (int b0 = 0; b0 < B; b0 += 4) {
-        const int nb = B - b0 < 4 ? B - b0 : 4;
-        float* vo = vertices + (size_t)b0 * n_coord;
-        const float* f = feat + (size_t)b0 * P;
-        const float* vs = v_shaped + (size_t)b0 * n_coord;
-        const float* Ab = A_skin + (size_t)b0 * m->J * 12;
-        const float* tb = transl ? transl + (size_t)3 * b0 : nullptr;
-        float* vp = saved ? saved + (size_t)b0 * n_coord : nullptr;
-        switch (nb) {
-            case 1: launch_skin<1>(m, vo, f, vs, Ab, tb, vp, s); break;
-            case 2: launch_skin<2>(m, vo, f, vs, Ab, tb, vp, s); break;
-            case 3: launch_skin<3>(m, vo, f, vs, Ab, tb, vp, s); break;
-            default: launch_skin<4>(m, vo, f, vs, Ab, tb, vp, s); break;
-        }
-    }
+    for_pose_runs(B, [&](int b0, auto nb) {
+        launch_skin<decltype(nb)::value>(m, vertices + (size_t)b0 * n_coord, feat + (size_t)b0 * P, v_shaped + (size_t)b0 * n_coord,
+                                         A_skin + (size_t)b0 * m->J * 12, transl ? transl + (size_t)3 * b0 : nullptr,
+                                         saved ? saved + (size_t)b0 * n_coord : nullptr, s);
+    });
     return check_hip(hipGetLastError(), "ag_smplx_forward");
 }
 
@@ -891,15 +890,8 @@ int ag_mat4_mul_inverse(float* out, const float* a, const float* b, int32_t n, i
 int ag_smplx_backward(const AgSmplxModel* m, int32_t B, const float* shape_components, const float* full_pose, const float* dL_dA,
                       const float* dL_djoints, float* dL_dfull_pose, float* dL_dtransl, float* dL_dshape_components, void* stream)
 {
-    if (!model_ok(m)) { set_error("smplx_backward: bad model (need 0 < J <= 64, non-null arrays)"); return AG_ERR_INVALID_ARGUMENT; }
-    if (!folded_ok(m)) { set_error("smplx_backward: joint_template / joint_dirs missing -- run ag_smplx_prepare once per model"); return AG_ERR_INVALID_ARGUMENT; }
-    if (B < 0) { set_error("smplx_backward: B < 0"); return AG_ERR_INVALID_ARGUMENT; }
-    if (B == 0) return AG_OK;
-    if (!full_pose || !dL_dfull_pose || (m->NB > 0 && !shape_components)) { set_error("smplx_backward: null pointer"); return AG_ERR_INVALID_ARGUMENT; }
-    hipLaunchKernelGGL(smplx_chain_backward_kernel<false>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), dL_dfull_pose, dL_dtransl,
-                       m->NB > 0 ? dL_dshape_components : nullptr, dL_dA, dL_djoints, full_pose, shape_components, m->joint_template,
-                       m->joint_dirs, m->parents, m->J, m->NB, nullptr, nullptr, nullptr, nullptr);
-    return check_hip(hipGetLastError(), "smplx_chain_backward_kernel");
+    return chain_backward_impl<false>("smplx_backward", m, B, shape_components, full_pose, dL_dA, dL_djoints, nullptr, nullptr, nullptr, nullptr,
+                                      dL_dfull_pose, dL_dtransl, dL_dshape_components, stream);
 }
 
 int ag_mat4_mul_inverse_backward(float* dL_da, float* dL_db, const float* dL_dout, const float* a, const float* b, int32_t n, int32_t b_batch,
@@ -958,9 +950,8 @@ int ag_smplx_vertex_backward(const AgSmplxModel* m, int32_t B, const float* save
                              float* dL_dfeat, float* dL_dtransl, float* dL_dshape_components, float* workspace, size_t workspace_floats,
                              void* stream)
 {
-    if (!model_ok(m)) { set_error("smplx_vertex_backward: bad model (need 0 < J <= 64, non-null arrays)"); return AG_ERR_INVALID_ARGUMENT; }
-    if (B < 0) { set_error("smplx_vertex_backward: B < 0"); return AG_ERR_INVALID_ARGUMENT; }
-    if (B == 0) return AG_OK;
+    int rc;
+    if (call_is_over("smplx_vertex_backward", m, B, false, &rc)) return rc;
     if (!saved || !dL_dvertices || !dL_dA_skin || !dL_dtransl || !workspace || (m->J > 1 && !dL_dfeat) || (m->NB > 0 && !dL_dshape_components)) {
         set_error("smplx_vertex_backward: null pointer");
         return AG_ERR_INVALID_ARGUMENT;
@@ -983,17 +974,10 @@ int ag_smplx_vertex_backward(const AgSmplxModel* m, int32_t B, const float* save
     hipLaunchKernelGGL(smplx_slab_sums_kernel, dim3(n_skin_blocks + (dirs_total + 15) / 16), dim3(256), 0, s, dL_dA_skin, dL_dtransl, skin_slabs,
                        n_slab, B, J, n_skin_blocks, dL_dshape_components, dirs_slabs, (int)vb_dirs_slabs(m), dirs_total);
     if (P > 0)
-        for (int b0 = 0; b0 < B; b0 += 4) {
-            const int nb = B - b0 < 4 ? B - b0 : 4;
-            float* df = dL_dfeat + (size_t)b0 * P;
-            const float* x = dvp + (size_t)b0 * n_coord;
-            switch (nb) {
-                case 1: hipLaunchKernelGGL(smplx_posedirs_t_kernel<1>, dim3(P), dim3(kPdThreads), 0, s, df, m->posedirs, x, n_coord, P); break;
-                case 2: hipLaunchKernelGGL(smplx_posedirs_t_kernel<2>, dim3(P), dim3(kPdThreads), 0, s, df, m->posedirs, x, n_coord, P); break;
-                case 3: hipLaunchKernelGGL(smplx_posedirs_t_kernel<3>, dim3(P), dim3(kPdThreads), 0, s, df, m->posedirs, x, n_coord, P); break;
-                default: hipLaunchKernelGGL(smplx_posedirs_t_kernel<4>, dim3(P), dim3(kPdThreads), 0, s, df, m->posedirs, x, n_coord, P); break;
-            }
-        }
+        for_pose_runs(B, [&](int b0, auto nb) {
+            hipLaunchKernelGGL(smplx_posedirs_t_kernel<decltype(nb)::value>, dim3(P), dim3(kPdThreads), 0, s, dL_dfeat + (size_t)b0 * P, m->posedirs,
+                               dvp + (size_t)b0 * n_coord, n_coord, P);
+        });
     return check_hip(hipGetLastError(), "ag_smplx_vertex_backward");
 }
 
@@ -1023,16 +1007,8 @@ int ag_smplx_backward_full(const AgSmplxModel* m, int32_t B, const float* shape_
                            const float* dL_dshape_components_add, float* dL_dfull_pose, float* dL_dtransl, float* dL_dshape_components,
                            void* stream)
 {
-    if (!model_ok(m)) { set_error("smplx_backward_full: bad model (need 0 < J <= 64, non-null arrays)"); return AG_ERR_INVALID_ARGUMENT; }
-    if (!folded_ok(m)) { set_error("smplx_backward_full: joint_template / joint_dirs missing -- run ag_smplx_prepare once per model"); return AG_ERR_INVALID_ARGUMENT; }
-    if (B < 0) { set_error("smplx_backward_full: B < 0"); return AG_ERR_INVALID_ARGUMENT; }
-    if (B == 0) return AG_OK;
-    if (!full_pose || !dL_dfull_pose || (m->NB > 0 && !shape_components)) { set_error("smplx_backward_full: null pointer"); return AG_ERR_INVALID_ARGUMENT; }
-    hipLaunchKernelGGL(smplx_chain_backward_kernel<true>, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), dL_dfull_pose, dL_dtransl,
-                       m->NB > 0 ? dL_dshape_components : nullptr, dL_dA, dL_djoints, full_pose, shape_components, m->joint_template,
-                       m->joint_dirs, m->parents, m->J, m->NB, dL_dA_skin, dL_dfeat, dL_dtransl_add,
-                       m->NB > 0 ? dL_dshape_components_add : nullptr);
-    return check_hip(hipGetLastError(), "smplx_chain_backward_kernel");
+    return chain_backward_impl<true>("smplx_backward_full", m, B, shape_components, full_pose, dL_dA, dL_djoints, dL_dA_skin, dL_dfeat,
+                                     dL_dtransl_add, dL_dshape_components_add, dL_dfull_pose, dL_dtransl, dL_dshape_components, stream);
 }
 
 }  // extern "C"

@@ -99,13 +99,6 @@ __global__ void __launch_bounds__(256) noise_bias_act_forward_kernel(float* __re
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // partials: [G * C * chunks][2] = (sum gx, sum gx * noise) of every workgroup, followed by [G * C * chunks] = max |gx| (the operand maximum
 // the fp16 split form of the convolutions that consume gx needs, ag_groups.h: taken here, the tensor is not read a second time for it)
 __global__ void __launch_bounds__(256) noise_bias_act_backward_kernel(float* __restrict__ gx, const float* __restrict__ gy,

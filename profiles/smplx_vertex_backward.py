@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Workload for the kernel trace of the SMPL-X vertex backward: forward + backward of a loss on the vertices, all 127 joints and A on a
-``vertex_grad`` model, B poses per call.  Run it under the profiler, one run per batch size:
+``vertex_grad`` model, B poses per call, then the chain alone, then the dataset path (`data_item`).  Run it under the profiler, one run per batch size:
 `rocprofv3 --kernel-trace --stats -f csv -d OUT -- python profiles/smplx_vertex_backward.py B`; the yardstick for the new backward
 kernels is `smplx_skin_kernel<B>` (the forward's pass over the same 61-MB basis) in the same trace."""
 import os
@@ -30,5 +30,10 @@ for i in range(5 + 50):          # the chain alone (a loss on A): smplx_chain_ba
     (out.A * wA).sum().backward()
     for v in x.values():
         v.grad = None
+params = synth.smplx_pose_params(n=1)     # the dataset path (no autograd): smplx_skin_kernel<3> and mat4_mul_inverse_kernel
+cano = torch.zeros(75)
+with torch.no_grad():
+    for i in range(5 + 50):
+        model.data_item(params, 0, cano[3:6], cano[:3], cano[6:69])
 torch.cuda.synchronize()
-print(f"B={B}: 2 x 55 forward + backward iterations done")
+print(f"B={B}: 2 x 55 forward + backward iterations and 55 data items done")

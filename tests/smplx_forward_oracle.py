@@ -94,14 +94,34 @@ def _chain_child_first(R, Jrest, parents):
     return G[:, :, :3, 3], A
 
 
-def forward_generic(m, comps, full_pose, transl=None, mutant=None):
+def _chain_as_list(R, Jrest, parents):
+    """smplx_oracle.rigid_chain for autograd: that one fills its [B, J, 4, 4] chain in place while later joints read earlier rows, which
+    autograd refuses to differentiate.  Same products in the same order, the chain kept as a list and A put together by concatenation
+    (test_pose_grad_gpu._smplx_chain_oracle does this for the standard model): the values are those of rigid_chain exactly."""
+    B, Jn = R.shape[:2]
+    bottom = torch.zeros(B, 1, 4, dtype=R.dtype)
+    bottom[..., 3] = 1
+    G = []
+    for j in range(Jn):
+        p = int(parents[j])
+        t = Jrest[:, j] - (Jrest[:, p] if p >= 0 else 0)
+        M = torch.cat([torch.cat([R[:, j], t[..., None]], 2), bottom], 1)
+        G.append(M if p < 0 else G[p] @ M)
+    G = torch.stack(G, 1)
+    rel = G[:, :, :3, 3] - (G[:, :, :3, :3] @ Jrest[..., None])[..., 0]
+    return G[:, :, :3, 3], torch.cat([torch.cat([G[:, :, :3, :3], rel[..., None]], 3), G[:, :, 3:]], 2)
+
+
+def forward_generic(m, comps, full_pose, transl=None, mutant=None, differentiable=False):
     """m: v_template [V,3], dirs [V,3,NB] (or shapedirs + expr_dirs, as smplx_oracle.model_tensors keeps them), posedirs [9(J-1), 3V],
     J_regressor [J,V], parents [J], lbs_weights [V,J], all of one dtype.  comps [B,NB]; full_pose [B,J,3] or [B,3J] with the pose mean
     already added; transl [B,3] or None.  Returns v_shaped, v_posed, rest joints, pose_feature, A_skin (before transl), A, joints
     (posed, [B,J,3]), vertices and `skinned` (the vertices before transl), in the arithmetic and order of smplx_oracle.forward.
-    `mutant`: one of the in-model MUTANTS."""
+    `mutant`: one of the in-model MUTANTS.  `differentiable`: the chain through `_chain_as_list`, so that torch autograd runs through
+    the result (same values)."""
     from oracle import smplx_oracle as so
     assert mutant in (None, "feature_joint", "transl_not_on_joints", "child_first"), mutant
+    assert not (differentiable and mutant == "child_first")
     dt = m['v_template'].dtype
     dirs = _dirs(m)
     V, Jn = dirs.shape[0], m['J_regressor'].shape[0]
@@ -117,7 +137,8 @@ def forward_generic(m, comps, full_pose, transl=None, mutant=None):
     else:
         feat = (R[:, 1:] - eye).reshape(B, -1)
     v_posed = v_shaped + (feat @ m['posedirs']).reshape(B, V, 3)
-    Jposed, A = (_chain_child_first if mutant == "child_first" else so.rigid_chain)(R, Jrest, m['parents'])
+    chain = _chain_child_first if mutant == "child_first" else _chain_as_list if differentiable else so.rigid_chain
+    Jposed, A = chain(R, Jrest, m['parents'])
     A_skin = A
     T = (m['lbs_weights'] @ A.reshape(B, -1, 16)).reshape(B, V, 4, 4)
     verts = skinned = (T[..., :3, :3] @ v_posed[..., None])[..., 0] + T[..., :3, 3]
@@ -381,6 +402,29 @@ def small_case(V, J, NB, tree, B):
         case['joint_template' + tag] = m['J_regressor'] @ m['v_template']
         case['joint_dirs' + tag] = torch.einsum('jv,vcl->jcl', m['J_regressor'], m['dirs'])
     return case
+
+
+@functools.lru_cache(maxsize=None)
+def small_case_gradients(V, J, NB, tree, B, with_transl):
+    """Torch autograd through `forward_generic(..., differentiable=True)` on one GRID_SMALL row (its model, components and pose; a transl
+    of this function's own, or None), in float64 and float32, for two losses with seeded weights:
+      chain  sum(A wA) + sum(joints wJ)                 what ag_smplx_backward differentiates
+      full   chain + sum(vertices wV)                   ag_smplx_vertex_backward -> ag_smplx_backward_full
+    Returns transl, wA [B,J,4,4] (row 3 meets the constant row of A: no gradient), wJ, wV and g[loss][dtype tag] = {pose, comps, transl
+    (None without transl)}.  Computed once, never modified."""
+    c = small_case(V, J, NB, tree, B)
+    g = torch.Generator().manual_seed(case_seed(V, J, NB, tree, B, "gradients"))
+    wA, wJ, wV = torch.randn(B, J, 4, 4, generator=g), torch.randn(B, J, 3, generator=g), torch.randn(B, V, 3, generator=g)
+    transl = torch.randn(B, 3, generator=g) * 0.5 if with_transl else None
+    out = {'transl': transl, 'wA': wA, 'wJ': wJ, 'wV': wV, 'chain': {}, 'full': {}}
+    for tag, dt in (('64', torch.float64), ('32', torch.float32)):
+        x = [t.detach().to(dt).clone().requires_grad_(True) for t in (c['pose'], c['comps']) + ((transl,) if with_transl else ())]
+        o = forward_generic(c['m' + tag], x[1], x[0], x[2] if with_transl else None, differentiable=True)
+        chain = (o['A'] * wA.to(dt)).sum() + (o['joints'] * wJ.to(dt)).sum()
+        for loss, L in (('chain', chain), ('full', chain + (o['vertices'] * wV.to(dt)).sum())):
+            gr = torch.autograd.grad(L, x, retain_graph=True)
+            out[loss][tag] = {'pose': gr[0], 'comps': gr[1], 'transl': gr[2] if with_transl else None}
+    return out
 
 
 ITEM_KEYS = ("live_smpl_v", "cano_smpl_v", "live_smpl_v_woRoot", "joints", "cano_jnts", "cano2live_jnt_mats", "cano2live_jnt_mats_woRoot")

@@ -129,6 +129,30 @@ def test_float32_oracle_is_a_measurement_on_the_small_grid(row):
             assert len(np.unique(idx)) < idx.size // 2, "vertex ids repeat across key points"
 
 
+@pytest.mark.parametrize("row", fo.GRID_SMALL, ids=lambda c: "-".join(str(x) for x in c))
+def test_differentiable_oracle_equals_the_in_place_one_and_its_gradients_are_a_measurement(row):
+    """forward_generic(differentiable=True) -- the chain as a list -- returns the in-place form's values exactly, in both dtypes; all
+    eight trees have parents[j] < j (the kernel's child gather walks c = j + 1 .. J); the float32 autograd gradients of
+    `small_case_gradients` differ from the float64 ones on every row, so the bar of the GPU test is no constant."""
+    import torch
+    V, J, NB, tree, B = row
+    c = fo.small_case(*row)
+    par = c['arrays']['parents']
+    assert par[0] == -1 and all(0 <= par[j] < j for j in range(1, J))
+    for tag in ('64', '32'):
+        o = fo.forward_generic(c['m' + tag], c['comps'], c['pose'], c['transl'], differentiable=True)
+        for k, v in c['o' + tag].items():
+            assert torch.equal(o[k], v), f"{row} float{tag}: {k} of the list-based chain differs from the in-place one"
+    for with_transl in (True, False):
+        g = fo.small_case_gradients(*row, with_transl)
+        for loss in ('chain', 'full'):
+            names = ['pose'] + (['comps'] if NB > 0 else []) + (['transl'] if with_transl else [])
+            ds = {k: _d32(f"{row} {loss} d{k}", g[loss]['64'][k], g[loss]['32'][k]) / float(g[loss]['64'][k].abs().max()) for k in names}
+            print(row, f"transl={with_transl}", loss, " ".join(f"d{k} {d:.2e}" for k, d in ds.items()))
+            assert max(ds.values()) < 1e-3, "float32 autograd loses more than 1e-3 of a gradient's scale: the oracle itself is off"
+            assert (g[loss]['64']['transl'] is None) == (not with_transl) and g[loss]['64']['comps'].shape == (B, NB)
+
+
 def test_float32_oracle_is_a_measurement_on_the_data_item():
     import torch
     from oracle import smplx_oracle as so
