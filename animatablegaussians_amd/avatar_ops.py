@@ -16,7 +16,8 @@ from ._lib import stream as _stream
 
 
 def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+    """The tensor's device pointer; None gives the null pointer."""
+    return ctypes.c_void_p(None if t is None else t.data_ptr())
 
 
 def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -30,49 +31,52 @@ def mask_to_pix(mask: torch.Tensor) -> torch.Tensor:
     return torch.nonzero(mask.reshape(-1), as_tuple=False).reshape(-1).to(torch.int32).contiguous()
 
 
+def _gather_args(pix, S, fields):
+    """``AgGatherArgs`` over the pixel list, with the tensors of ``fields`` (a dict, or (name, tensor) pairs) in their pointer slots.  A slot
+    that is not named stays null: that part is not computed, or its network map counts as all zero (include/ag_avatar.h)."""
+    a = _lib.AgGatherArgs()
+    a.N, a.S, a.pix = int(pix.numel()), int(S), _p(pix)
+    for name, t in dict(fields).items():
+        setattr(a, name, _p(t))
+    return a
+
+
+def _gather_call(entry, dev, a, *grad_maps):
+    """``ag_gather_activate_forward`` / ``_backward`` (the latter with its three gradient maps, None for one that is not wanted)."""
+    with _lib.on_device(dev):
+        _lib.check(getattr(_lib.lib(), entry)(ctypes.byref(a), *(_p(m) for m in grad_maps), _stream(dev)), entry)
+
+
+def _grads_or_zeros(grads, widths, N, dev):
+    return [(_chk(g, "grad") if g is not None else torch.zeros((N, c), dtype=torch.float32, device=dev)) for g, c in zip(grads, widths)]
+
+
+_GATHER_IN = ("position_map", "other_map", "color_map", "xyz", "opacity_raw", "scaling_raw", "rotation_raw")
+_GATHER_OUT = ("positions", "opacity", "scales", "rotations", "colors")
+
+
 class _GatherActivate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, position_map, other_map, color_map, pix, xyz, opacity_raw, scaling_raw, rotation_raw):
-        L = _lib.lib()
-        position_map, other_map, color_map = (_chk(position_map, "position_map"), _chk(other_map, "other_map"),
-                                              _chk(color_map, "color_map"))
-        xyz, opacity_raw = _chk(xyz, "xyz"), _chk(opacity_raw, "opacity_raw")
-        scaling_raw, rotation_raw = _chk(scaling_raw, "scaling_raw"), _chk(rotation_raw, "rotation_raw")
+        ins = [_chk(t, name) for name, t in zip(_GATHER_IN, (position_map, other_map, color_map, xyz, opacity_raw, scaling_raw, rotation_raw))]
+        position_map, other_map, color_map = ins[:3]
         S = int(position_map.shape[-1])
         if tuple(position_map.shape) != (1, 6, S, S) or tuple(other_map.shape) != (1, 16, S, S) or tuple(color_map.shape) != (1, 6, S, S):
             raise RuntimeError("expected maps of shape [1,6,S,S], [1,16,S,S], [1,6,S,S]")
         N, dev = int(pix.numel()), position_map.device
-        f = dict(dtype=torch.float32, device=dev)
-        out = [torch.empty((N, c), **f) for c in (3, 1, 3, 4, 3)]
-        a = _lib.AgGatherArgs()
-        a.N, a.S = N, S
-        a.pix = _p(pix)
-        a.position_map, a.other_map, a.color_map = _p(position_map), _p(other_map), _p(color_map)
-        a.xyz, a.opacity_raw, a.scaling_raw, a.rotation_raw = _p(xyz), _p(opacity_raw), _p(scaling_raw), _p(rotation_raw)
-        a.positions, a.opacity, a.scales, a.rotations, a.colors = (_p(t) for t in out)
-        with _lib.on_device(dev):
-            _lib.check(L.ag_gather_activate_forward(ctypes.byref(a), _stream(dev)), "ag_gather_activate_forward")
-        ctx.save_for_backward(position_map, other_map, color_map, pix, xyz, opacity_raw, scaling_raw, rotation_raw)
+        out = [torch.empty((N, c), dtype=torch.float32, device=dev) for c in (3, 1, 3, 4, 3)]
+        _gather_call("ag_gather_activate_forward", dev, _gather_args(pix, S, zip(_GATHER_IN + _GATHER_OUT, ins + out)))
+        ctx.save_for_backward(*ins[:3], pix, *ins[3:])
         return tuple(out)
 
     @staticmethod
     def backward(ctx, g_pos, g_opa, g_sca, g_rot, g_col):
-        L = _lib.lib()
-        position_map, other_map, color_map, pix, xyz, opacity_raw, scaling_raw, rotation_raw = ctx.saved_tensors
+        position_map, other_map, color_map, pix, *raws = ctx.saved_tensors
         dev = position_map.device
-        N, S = int(pix.numel()), int(position_map.shape[-1])
-        grads = [(_chk(g, "grad") if g is not None else torch.zeros((N, c), dtype=torch.float32, device=dev))
-                 for g, c in ((g_pos, 3), (g_opa, 1), (g_sca, 3), (g_rot, 4), (g_col, 3))]
-        a = _lib.AgGatherArgs()
-        a.N, a.S = N, S
-        a.pix = _p(pix)
-        a.position_map, a.other_map, a.color_map = _p(position_map), _p(other_map), _p(color_map)
-        a.xyz, a.opacity_raw, a.scaling_raw, a.rotation_raw = _p(xyz), _p(opacity_raw), _p(scaling_raw), _p(rotation_raw)
-        a.positions, a.opacity, a.scales, a.rotations, a.colors = (_p(t) for t in grads)
+        grads = _grads_or_zeros((g_pos, g_opa, g_sca, g_rot, g_col), (3, 1, 3, 4, 3), int(pix.numel()), dev)
+        a = _gather_args(pix, position_map.shape[-1], zip(_GATHER_IN + _GATHER_OUT, [position_map, other_map, color_map] + raws + grads))
         gp, go, gc = (torch.empty_like(m) for m in (position_map, other_map, color_map))
-        with _lib.on_device(dev):
-            _lib.check(L.ag_gather_activate_backward(ctypes.byref(a), _p(gp), _p(go), _p(gc), _stream(dev)),
-                       "ag_gather_activate_backward")
+        _gather_call("ag_gather_activate_backward", dev, a, gp, go, gc)
         # the canonical Gaussian parameters are not optimised by the reference trainer (GaussianModel is not an
         # nn.Module, main_avatar.py:55-58 only collects avatar_net.parameters()): no gradient is produced for them
         return gp, go, gc, None, None, None, None, None
@@ -88,59 +92,35 @@ class _GatherPart(torch.autograd.Function):
     network output (network/avatar.py:93-124), the way the reference trainer's pre-training pass calls them
     (main_avatar.py:126-160).  ``part`` in {'position', 'other', 'color'}; ``raws`` = the canonical parameters that part adds."""
 
-    _SHAPES = {"position": (6, (3,)), "other": (16, (1, 3, 4)), "color": (6, (3,))}
+    # part: channels of its map, the slots of its map, of its canonical parameters and of its outputs, the outputs' widths
+    _PARTS = {"position": (6, "position_map", ("xyz",), ("positions",), (3,)),
+              "other": (16, "other_map", ("opacity_raw", "scaling_raw", "rotation_raw"), ("opacity", "scales", "rotations"), (1, 3, 4)),
+              "color": (6, "color_map", (), ("colors",), (3,))}
 
     @staticmethod
     def forward(ctx, part, net_map, pix, *raws):
-        L = _lib.lib()
-        ch, outs = _GatherPart._SHAPES[part]
+        ch, map_slot, raw_slots, out_slots, widths = _GatherPart._PARTS[part]
         net_map = _chk(net_map, part + "_map")
         S = int(net_map.shape[-1])
         if tuple(net_map.shape) != (1, ch, S, S):
             raise RuntimeError(f"expected a {part} map of shape [1,{ch},S,S]")
-        raws = tuple(_chk(r, "canonical parameter") for r in raws)
+        raws = [_chk(r, "canonical parameter") for r in raws]
         N, dev = int(pix.numel()), net_map.device
-        out = [torch.empty((N, c), dtype=torch.float32, device=dev) for c in outs]
-        a = _lib.AgGatherArgs()
-        a.N, a.S, a.pix = N, S, _p(pix)
-        if part == "position":
-            a.position_map, a.xyz, a.positions = _p(net_map), _p(raws[0]), _p(out[0])
-        elif part == "other":
-            a.other_map = _p(net_map)
-            a.opacity_raw, a.scaling_raw, a.rotation_raw = (_p(r) for r in raws)
-            a.opacity, a.scales, a.rotations = (_p(t) for t in out)
-        else:
-            a.color_map, a.colors = _p(net_map), _p(out[0])
-        with _lib.on_device(dev):
-            _lib.check(L.ag_gather_activate_forward(ctypes.byref(a), _stream(dev)), "ag_gather_activate_forward")
+        out = [torch.empty((N, c), dtype=torch.float32, device=dev) for c in widths]
+        _gather_call("ag_gather_activate_forward", dev, _gather_args(pix, S, zip((map_slot,) + raw_slots + out_slots, [net_map] + raws + out)))
         ctx.part = part
         ctx.save_for_backward(net_map, pix, *raws)
         return tuple(out)
 
     @staticmethod
     def backward(ctx, *grads):
-        L = _lib.lib()
         net_map, pix, *raws = ctx.saved_tensors
-        part, dev = ctx.part, net_map.device
-        N, S = int(pix.numel()), int(net_map.shape[-1])
-        outs = _GatherPart._SHAPES[part][1]
-        grads = [(_chk(g, "grad") if g is not None else torch.zeros((N, c), dtype=torch.float32, device=dev)) for g, c in zip(grads, outs)]
+        _, map_slot, raw_slots, out_slots, widths = _GatherPart._PARTS[ctx.part]
+        dev = net_map.device
+        grads = _grads_or_zeros(grads, widths, int(pix.numel()), dev)
+        a = _gather_args(pix, net_map.shape[-1], zip((map_slot,) + raw_slots + out_slots, [net_map] + raws + grads))
         gm = torch.empty_like(net_map)
-        a = _lib.AgGatherArgs()
-        a.N, a.S, a.pix = N, S, _p(pix)
-        null = ctypes.c_void_p(None)
-        gp = go = gc = null
-        if part == "position":
-            a.positions, gp = _p(grads[0]), _p(gm)
-        elif part == "other":
-            a.other_map = _p(net_map)
-            a.opacity_raw, a.scaling_raw, a.rotation_raw = (_p(r) for r in raws)
-            a.opacity, a.scales, a.rotations = (_p(t) for t in grads)
-            go = _p(gm)
-        else:
-            a.colors, gc = _p(grads[0]), _p(gm)
-        with _lib.on_device(dev):
-            _lib.check(L.ag_gather_activate_backward(ctypes.byref(a), gp, go, gc, _stream(dev)), "ag_gather_activate_backward")
+        _gather_call("ag_gather_activate_backward", dev, a, *(gm if p == ctx.part else None for p in _GatherPart._PARTS))
         return (None, gm, None) + (None,) * len(raws)
 
 
@@ -164,13 +144,9 @@ def canonical_activations(pix, S, opacity_raw, scaling_raw, rotation_raw):
     """``GaussianModel.get_opacity / get_scaling / get_rotation`` (gaussians/gaussian_model.py:115-147): the activations of
     the canonical parameters alone (the assembly kernel with a null network map)."""
     N, dev = int(pix.numel()), opacity_raw.device
+    raws = [_chk(r, "canonical parameter") for r in (opacity_raw, scaling_raw, rotation_raw)]
     out = [torch.empty((N, c), dtype=torch.float32, device=dev) for c in (1, 3, 4)]
-    a = _lib.AgGatherArgs()
-    a.N, a.S, a.pix = N, int(S), _p(pix)
-    a.opacity_raw, a.scaling_raw, a.rotation_raw = (_p(_chk(r, "canonical parameter")) for r in (opacity_raw, scaling_raw, rotation_raw))
-    a.opacity, a.scales, a.rotations = (_p(t) for t in out)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().ag_gather_activate_forward(ctypes.byref(a), _stream(dev)), "ag_gather_activate_forward")
+    _gather_call("ag_gather_activate_forward", dev, _gather_args(pix, S, zip(_GATHER_IN[4:] + _GATHER_OUT[1:4], raws + out)))
     return tuple(out)
 
 
@@ -253,10 +229,8 @@ class _LbsTransform(torch.autograd.Function):
         dj = torch.empty_like(jnt_mats)
         ws_bytes = int(L.ag_lbs_backward_joints_workspace_bytes(N, J))
         ws = torch.empty((max(ws_bytes // 4, 1),), dtype=torch.float32, device=dev)
-        null = ctypes.c_void_p(None)
         with _lib.on_device(dev):
-            _lib.check(L.ag_lbs_backward_joints(ctypes.byref(a), _p(dp) if dp is not None else null, _p(dr) if dr is not None else null,
-                                                _p(dj), _p(ws), ws_bytes, _stream(dev)), "ag_lbs_backward_joints")
+            _lib.check(L.ag_lbs_backward_joints(ctypes.byref(a), _p(dp), _p(dr), _p(dj), _p(ws), ws_bytes, _stream(dev)), "ag_lbs_backward_joints")
         return (dp if ctx.needs_input_grad[0] else None), (dr if ctx.needs_input_grad[1] else None), None, dj, None
 
 

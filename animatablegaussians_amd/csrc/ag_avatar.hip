@@ -166,165 +166,87 @@ __device__ __forceinline__ void quat_to_mat(const float (&q)[4], float (&R)[9], 
     R[6] = two_s * (i * k - j * r);     R[7] = two_s * (j * k + i * r);     R[8] = 1 - two_s * (i * i + j * j);
 }
 
+// The rotation head of one Gaussian, the part of the forward that the backward has to recompute bit for bit: R(q), m = M3 * R, then
+// pytorch3d 0.7.4 matrix_to_quaternion up to its candidate row -- sqrt of the positive part, arg-max candidate, no sign fix.  The
+// division by 2 max(qa[best], 0.1) is the caller's.  Everything lands in the caller's locals: returned as a struct, the dynamically
+// indexed qa[best] puts the whole head into scratch ('Skinning kernels: what is stated once').
+__device__ __forceinline__ void rotation_head(const float (&q)[4], const float (&M)[12], float (&R)[9], float& two_s, float (&m)[9],
+                                              float (&x4)[4], float (&qa)[4], float (&cand)[4], int& best)
+{
+    quat_to_mat(q, R, two_s);
+    // m = M3 * R = M[4x] R[z] + M[4x + 1] R[3 + z] + M[4x + 2] R[6 + z] with its fusing written out.  Left to -ffp-contract=fast, which of the
+    // first two products stays a multiplication depends on how far the caller is optimised when this is inlined: lbs_backward_joints_kernel
+    // used to get the other pairing in m[0], m[3], m[6] than the forward it recomputes.  This is the pairing lbs_forward_kernel always had.
+#pragma unroll
+    for (int x = 0; x < 3; x++)
+#pragma unroll
+        for (int z = 0; z < 3; z++) m[3 * x + z] = fmaf(M[4 * x + 2], R[6 + z], fmaf(M[4 * x], R[z], M[4 * x + 1] * R[3 + z]));
+    x4[0] = 1.0f + m[0] + m[4] + m[8]; x4[1] = 1.0f + m[0] - m[4] - m[8]; x4[2] = 1.0f - m[0] + m[4] - m[8]; x4[3] = 1.0f - m[0] - m[4] + m[8];
+#pragma unroll
+    for (int c = 0; c < 4; c++) qa[c] = x4[c] > 0.f ? sqrtf(x4[c]) : 0.f;
+    best = 0;
+#pragma unroll
+    for (int c = 1; c < 4; c++) if (qa[c] > qa[best]) best = c;
+    if (best == 0)      { cand[0] = qa[0] * qa[0]; cand[1] = m[7] - m[5]; cand[2] = m[2] - m[6]; cand[3] = m[3] - m[1]; }
+    else if (best == 1) { cand[0] = m[7] - m[5]; cand[1] = qa[1] * qa[1]; cand[2] = m[3] + m[1]; cand[3] = m[2] + m[6]; }
+    else if (best == 2) { cand[0] = m[2] - m[6]; cand[1] = m[3] + m[1]; cand[2] = qa[2] * qa[2]; cand[3] = m[5] + m[7]; }
+    else                { cand[0] = m[3] - m[1]; cand[1] = m[6] + m[2]; cand[2] = m[7] + m[5]; cand[3] = qa[3] * qa[3]; }
+}
+
+// What lbs_forward_kernel and lbs_backward_kernel start with: the wave's 64 weight rows staged in its LDS slab (dense) and the lane's
+// Gaussian n with its blended matrix M.  False for a wave past N (before it stages anything) and for a lane past N (after its wave has
+// staged): the kernel returns.
 template <bool SPARSE>
-__global__ void __launch_bounds__(256) lbs_forward_kernel(AgLbsArgs a)
+__device__ __forceinline__ bool lbs_lane_matrix(const AgLbsArgs& a, int& n, float (&M)[12])
 {
     extern __shared__ float lds[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int first = (blockIdx.x * 4 + wave) * 64;
-    if (first >= a.N) return;
-    const int n = first + lane;
-    float M[12];
+    if (first >= a.N) return false;
+    n = first + lane;
     if constexpr (SPARSE) {
-        if (n >= a.N) return;
+        if (n >= a.N) return false;
         blend_matrix_sparse(a.sp_idx, a.sp_w, a.K, a.N, n, a.jnt_mats, M);
     } else {
         float* slab = lds + (size_t)wave * 64 * a.J;
         stage_rows(a.lbs, a.N, a.J, first, slab, lane);
-        if (n >= a.N) return;
+        if (n >= a.N) return false;
         blend_matrix(slab + lane * a.J, a.jnt_mats, a.J, M);
     }
+    return true;
+}
+
+template <bool SPARSE>
+__global__ void __launch_bounds__(256) lbs_forward_kernel(AgLbsArgs a)
+{
+    int n;
+    float M[12];
+    if (!lbs_lane_matrix<SPARSE>(a, n, M)) return;
     const float px = a.positions[3 * n], py = a.positions[3 * n + 1], pz = a.positions[3 * n + 2];
     a.out_positions[3 * n + 0] = M[0] * px + M[1] * py + M[2] * pz + M[3];
     a.out_positions[3 * n + 1] = M[4] * px + M[5] * py + M[6] * pz + M[7];
     a.out_positions[3 * n + 2] = M[8] * px + M[9] * py + M[10] * pz + M[11];
 
     float q[4] = { a.rotations[4 * n], a.rotations[4 * n + 1], a.rotations[4 * n + 2], a.rotations[4 * n + 3] };
-    float R[9], two_s;
-    quat_to_mat(q, R, two_s);
-    float m[9];   // m = M3 * R
-#pragma unroll
-    for (int x = 0; x < 3; x++)
-#pragma unroll
-        for (int z = 0; z < 3; z++) m[3 * x + z] = M[4 * x] * R[z] + M[4 * x + 1] * R[3 + z] + M[4 * x + 2] * R[6 + z];
-    // pytorch3d 0.7.4 matrix_to_quaternion: sqrt of the positive part, arg-max candidate, 0.1 floor, no sign fix
-    const float x4[4] = { 1.0f + m[0] + m[4] + m[8], 1.0f + m[0] - m[4] - m[8], 1.0f - m[0] + m[4] - m[8], 1.0f - m[0] - m[4] + m[8] };
-    float qa[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) qa[c] = x4[c] > 0.f ? sqrtf(x4[c]) : 0.f;
-    int best = 0;
-#pragma unroll
-    for (int c = 1; c < 4; c++) if (qa[c] > qa[best]) best = c;
-    float cand[4];
-    if (best == 0)      { cand[0] = qa[0] * qa[0]; cand[1] = m[7] - m[5]; cand[2] = m[2] - m[6]; cand[3] = m[3] - m[1]; }
-    else if (best == 1) { cand[0] = m[7] - m[5]; cand[1] = qa[1] * qa[1]; cand[2] = m[3] + m[1]; cand[3] = m[2] + m[6]; }
-    else if (best == 2) { cand[0] = m[2] - m[6]; cand[1] = m[3] + m[1]; cand[2] = qa[2] * qa[2]; cand[3] = m[5] + m[7]; }
-    else                { cand[0] = m[3] - m[1]; cand[1] = m[6] + m[2]; cand[2] = m[7] + m[5]; cand[3] = qa[3] * qa[3]; }
-    const float den = 2.0f * fmaxf(qa[best], 0.1f);
+    float R[9], two_s, m[9], x4[4], qa[4], cand[4];
+    int best;
+    rotation_head(q, M, R, two_s, m, x4, qa, cand, best);
+    const float den = 2.0f * fmaxf(qa[best], 0.1f);      // the 0.1 floor
 #pragma unroll
     for (int c = 0; c < 4; c++) a.out_rotations[4 * n + c] = cand[c] / den;
 }
 
-template <bool SPARSE>
-__global__ void __launch_bounds__(256) lbs_backward_kernel(AgLbsArgs a, float* __restrict__ g_positions,
-                                                          float* __restrict__ g_rotations)
-{
-    extern __shared__ float lds[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int first = (blockIdx.x * 4 + wave) * 64;
-    if (first >= a.N) return;
-    const int n = first + lane;
-    float M[12];
-    if constexpr (SPARSE) {
-        if (n >= a.N) return;
-        blend_matrix_sparse(a.sp_idx, a.sp_w, a.K, a.N, n, a.jnt_mats, M);
-    } else {
-        float* slab = lds + (size_t)wave * 64 * a.J;
-        stage_rows(a.lbs, a.N, a.J, first, slab, lane);
-        if (n >= a.N) return;
-        blend_matrix(slab + lane * a.J, a.jnt_mats, a.J, M);
-    }
-
-    // positions: dL/dp = M3^T g
-    const float gx = a.out_positions[3 * n], gy = a.out_positions[3 * n + 1], gz = a.out_positions[3 * n + 2];
-    g_positions[3 * n + 0] = M[0] * gx + M[4] * gy + M[8] * gz;
-    g_positions[3 * n + 1] = M[1] * gx + M[5] * gy + M[9] * gz;
-    g_positions[3 * n + 2] = M[2] * gx + M[6] * gy + M[10] * gz;
-
-    // rotations: recompute the forward, then walk the chain backwards
-    float q[4] = { a.rotations[4 * n], a.rotations[4 * n + 1], a.rotations[4 * n + 2], a.rotations[4 * n + 3] };
-    float R[9], two_s;
-    quat_to_mat(q, R, two_s);
-    float m[9];
-#pragma unroll
-    for (int x = 0; x < 3; x++)
-#pragma unroll
-        for (int z = 0; z < 3; z++) m[3 * x + z] = M[4 * x] * R[z] + M[4 * x + 1] * R[3 + z] + M[4 * x + 2] * R[6 + z];
-    const float x4[4] = { 1.0f + m[0] + m[4] + m[8], 1.0f + m[0] - m[4] - m[8], 1.0f - m[0] + m[4] - m[8], 1.0f - m[0] - m[4] + m[8] };
-    float qa[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) qa[c] = x4[c] > 0.f ? sqrtf(x4[c]) : 0.f;
-    int best = 0;
-#pragma unroll
-    for (int c = 1; c < 4; c++) if (qa[c] > qa[best]) best = c;
-    float cand[4];
-    if (best == 0)      { cand[0] = qa[0] * qa[0]; cand[1] = m[7] - m[5]; cand[2] = m[2] - m[6]; cand[3] = m[3] - m[1]; }
-    else if (best == 1) { cand[0] = m[7] - m[5]; cand[1] = qa[1] * qa[1]; cand[2] = m[3] + m[1]; cand[3] = m[2] + m[6]; }
-    else if (best == 2) { cand[0] = m[2] - m[6]; cand[1] = m[3] + m[1]; cand[2] = qa[2] * qa[2]; cand[3] = m[5] + m[7]; }
-    else                { cand[0] = m[3] - m[1]; cand[1] = m[6] + m[2]; cand[2] = m[7] + m[5]; cand[3] = qa[3] * qa[3]; }
-    const float qsel = qa[best];
-    const bool floored = !(qsel > 0.1f);
-    const float den = 2.0f * (floored ? 0.1f : qsel);
-    float go[4] = { a.out_rotations[4 * n], a.out_rotations[4 * n + 1], a.out_rotations[4 * n + 2], a.out_rotations[4 * n + 3] };
-    // out = cand / den
-    float gc[4], gden = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; c++) { gc[c] = go[c] / den; gden -= go[c] * cand[c] / (den * den); }
-    // den = 2 max(q_sel, 0.1): no gradient when the floor is active; the diagonal candidate is q_sel^2
-    float gq_sel = floored ? 0.f : 2.0f * gden;
-    gq_sel += 2.0f * qsel * gc[best];
-    // q_sel = sqrt(max(0, x_sel)) (zero sub-gradient at x <= 0)
-    const float gx_sel = (x4[best] > 0.f) ? gq_sel / (2.0f * qsel) : 0.f;
-    float gm[9];
-#pragma unroll
-    for (int c = 0; c < 9; c++) gm[c] = 0.f;
-    const float s0 = (best == 0 || best == 1) ? 1.f : -1.f;   // sign of m00 in x_best
-    const float s1 = (best == 0 || best == 2) ? 1.f : -1.f;   // sign of m11
-    const float s2 = (best == 0 || best == 3) ? 1.f : -1.f;   // sign of m22
-    gm[0] += s0 * gx_sel; gm[4] += s1 * gx_sel; gm[8] += s2 * gx_sel;
-    if (best == 0)      { gm[7] += gc[1]; gm[5] -= gc[1]; gm[2] += gc[2]; gm[6] -= gc[2]; gm[3] += gc[3]; gm[1] -= gc[3]; }
-    else if (best == 1) { gm[7] += gc[0]; gm[5] -= gc[0]; gm[3] += gc[2]; gm[1] += gc[2]; gm[2] += gc[3]; gm[6] += gc[3]; }
-    else if (best == 2) { gm[2] += gc[0]; gm[6] -= gc[0]; gm[3] += gc[1]; gm[1] += gc[1]; gm[5] += gc[3]; gm[7] += gc[3]; }
-    else                { gm[3] += gc[0]; gm[1] -= gc[0]; gm[6] += gc[1]; gm[2] += gc[1]; gm[7] += gc[2]; gm[5] += gc[2]; }
-    // m = M3 R  ->  dL/dR = M3^T gm
-    float G[9];
-#pragma unroll
-    for (int y = 0; y < 3; y++)
-#pragma unroll
-        for (int z = 0; z < 3; z++) G[3 * y + z] = M[y] * gm[z] + M[4 + y] * gm[3 + z] + M[8 + y] * gm[6 + z];
-    // R = I + two_s * U(q); dL/dq = two_s * dU^T G - two_s^2 q (U . G)
-    const float r = q[0], i = q[1], j = q[2], k = q[3];
-    const float U[9] = { -(j * j + k * k), i * j - k * r, i * k + j * r,
-                         i * j + k * r, -(i * i + k * k), j * k - i * r,
-                         i * k - j * r, j * k + i * r, -(i * i + j * j) };
-    float gs = 0.f;
-#pragma unroll
-    for (int c = 0; c < 9; c++) gs += G[c] * U[c];
-    const float dr = -k * G[1] + j * G[2] + k * G[3] - i * G[5] - j * G[6] + i * G[7];
-    const float di = j * G[1] + k * G[2] + j * G[3] - 2 * i * G[4] - r * G[5] + k * G[6] + r * G[7] - 2 * i * G[8];
-    const float dj = -2 * j * G[0] + i * G[1] + r * G[2] + i * G[3] + k * G[5] - r * G[6] + k * G[7] - 2 * j * G[8];
-    const float dk = -2 * k * G[0] - r * G[1] + i * G[2] + r * G[3] - 2 * k * G[4] + j * G[5] + i * G[6] + j * G[7];
-    const float t2 = two_s * two_s * gs;
-    g_rotations[4 * n + 0] = two_s * dr - t2 * r;
-    g_rotations[4 * n + 1] = two_s * di - t2 * i;
-    g_rotations[4 * n + 2] = two_s * dj - t2 * j;
-    g_rotations[4 * n + 3] = two_s * dk - t2 * k;
-}
-
-// The chain of lbs_backward_kernel for one Gaussian with its blended matrix M, extended by GM[12] = dL/dM (3x4) with JOINTS -- the
-// per-Gaussian term of the joint-matrix gradient dL/dA_j = sum_n w_nj GM_n.  lbs_backward_joints_kernel calls it with null position /
-// rotation outputs: those come from lbs_backward_kernel itself (ag_lbs_backward_joints), so that they are ag_lbs_backward's bits.
+// The backward of one Gaussian with its blended matrix M; a.out_positions / a.out_rotations hold the upstream gradients.  What it
+// writes is fixed by the instantiation, so that dL/dq and dL/dA walk one text back from out = cand / den:
+//   JOINTS = false  dL/dpositions and dL/drotations to g_positions / g_rotations (lbs_backward_kernel); GM is not touched
+//   JOINTS = true   GM[12] = dL/dM (3x4), the per-Gaussian term of the joint-matrix gradient dL/dA_j = sum_n w_nj GM_n
+//                   (lbs_backward_joints_kernel); the two pointers are not touched -- those gradients come from lbs_backward_kernel's
+//                   own launch (ag_lbs_backward_joints), so that they are ag_lbs_backward's bits
 template <bool JOINTS>
 __device__ __forceinline__ void lbs_backward_gaussian(const AgLbsArgs& a, int n, const float (&M)[12], float* __restrict__ g_positions,
                                                       float* __restrict__ g_rotations, float (&GM)[12])
 {
-    // positions: dL/dp = M3^T g
     const float gx = a.out_positions[3 * n], gy = a.out_positions[3 * n + 1], gz = a.out_positions[3 * n + 2];
-    if (g_positions) {
-        g_positions[3 * n + 0] = M[0] * gx + M[4] * gy + M[8] * gz;
-        g_positions[3 * n + 1] = M[1] * gx + M[5] * gy + M[9] * gz;
-        g_positions[3 * n + 2] = M[2] * gx + M[6] * gy + M[10] * gz;
-    }
     if constexpr (JOINTS) {
         // live p = M3 p + M[:, 3]  ->  dL/dM = g (x) [p, 1]
         const float p[3] = { a.positions[3 * n], a.positions[3 * n + 1], a.positions[3 * n + 2] };
@@ -335,29 +257,18 @@ __device__ __forceinline__ void lbs_backward_gaussian(const AgLbsArgs& a, int n,
             for (int c = 0; c < 3; c++) GM[4 * r + c] = g[r] * p[c];
             GM[4 * r + 3] = g[r];
         }
+    } else {
+        // positions: dL/dp = M3^T g
+        g_positions[3 * n + 0] = M[0] * gx + M[4] * gy + M[8] * gz;
+        g_positions[3 * n + 1] = M[1] * gx + M[5] * gy + M[9] * gz;
+        g_positions[3 * n + 2] = M[2] * gx + M[6] * gy + M[10] * gz;
     }
 
     // rotations: recompute the forward, then walk the chain backwards
     float q[4] = { a.rotations[4 * n], a.rotations[4 * n + 1], a.rotations[4 * n + 2], a.rotations[4 * n + 3] };
-    float R[9], two_s;
-    quat_to_mat(q, R, two_s);
-    float m[9];
-#pragma unroll
-    for (int x = 0; x < 3; x++)
-#pragma unroll
-        for (int z = 0; z < 3; z++) m[3 * x + z] = M[4 * x] * R[z] + M[4 * x + 1] * R[3 + z] + M[4 * x + 2] * R[6 + z];
-    const float x4[4] = { 1.0f + m[0] + m[4] + m[8], 1.0f + m[0] - m[4] - m[8], 1.0f - m[0] + m[4] - m[8], 1.0f - m[0] - m[4] + m[8] };
-    float qa[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) qa[c] = x4[c] > 0.f ? sqrtf(x4[c]) : 0.f;
-    int best = 0;
-#pragma unroll
-    for (int c = 1; c < 4; c++) if (qa[c] > qa[best]) best = c;
-    float cand[4];
-    if (best == 0)      { cand[0] = qa[0] * qa[0]; cand[1] = m[7] - m[5]; cand[2] = m[2] - m[6]; cand[3] = m[3] - m[1]; }
-    else if (best == 1) { cand[0] = m[7] - m[5]; cand[1] = qa[1] * qa[1]; cand[2] = m[3] + m[1]; cand[3] = m[2] + m[6]; }
-    else if (best == 2) { cand[0] = m[2] - m[6]; cand[1] = m[3] + m[1]; cand[2] = qa[2] * qa[2]; cand[3] = m[5] + m[7]; }
-    else                { cand[0] = m[3] - m[1]; cand[1] = m[6] + m[2]; cand[2] = m[7] + m[5]; cand[3] = qa[3] * qa[3]; }
+    float R[9], two_s, m[9], x4[4], qa[4], cand[4];
+    int best;
+    rotation_head(q, M, R, two_s, m, x4, qa, cand, best);
     const float qsel = qa[best];
     const bool floored = !(qsel > 0.1f);
     const float den = 2.0f * (floored ? 0.1f : qsel);
@@ -388,8 +299,8 @@ __device__ __forceinline__ void lbs_backward_gaussian(const AgLbsArgs& a, int n,
         for (int x = 0; x < 3; x++)
 #pragma unroll
             for (int y = 0; y < 3; y++) GM[4 * x + y] += gm[3 * x] * R[3 * y] + gm[3 * x + 1] * R[3 * y + 1] + gm[3 * x + 2] * R[3 * y + 2];
+        return;
     }
-    if (!g_rotations) return;
     // m = M3 R  ->  dL/dR = M3^T gm
     float G[9];
 #pragma unroll
@@ -415,7 +326,18 @@ __device__ __forceinline__ void lbs_backward_gaussian(const AgLbsArgs& a, int n,
     g_rotations[4 * n + 3] = two_s * dk - t2 * k;
 }
 
-// Joint-matrix gradient, pass 1 (the blend and the rotation chain of lbs_backward_kernel again, plus the reduction of its workgroup): every workgroup writes its
+template <bool SPARSE>
+__global__ void __launch_bounds__(256) lbs_backward_kernel(AgLbsArgs a, float* __restrict__ g_positions,
+                                                          float* __restrict__ g_rotations)
+{
+    int n;
+    float M[12], no_gm[12];
+    if (!lbs_lane_matrix<SPARSE>(a, n, M)) return;
+    lbs_backward_gaussian<false>(a, n, M, g_positions, g_rotations, no_gm);
+}
+
+// Joint-matrix gradient, pass 1 (the blend and lbs_backward_gaussian<true>, plus the reduction of its workgroup; its own prologue, as its idle lanes stay to
+// the reduction): every workgroup writes its
 // slab [J][12] = sum over its 256 Gaussians of w_nj GM_n.  LDS: [4 waves][64][J] weight rows | [4][64][12] GM rows; the [J][12] partial of a wave goes over its
 // own weight rows once every lane has read its columns (12 J <= 64 J floats), which is what lets J = 140 fit: (256 J + 3072) * 4 B = 155648 B of the 163840.
 // The sparse form is expanded into the dense row layout (zeros, then its K weights), so both forms run the same summation over the same
@@ -547,6 +469,22 @@ __global__ void __launch_bounds__(256) hand_fuse_kernel(AgHandFuseArgs a)
     for (int c = 0; c < 4; ++c) a.rotations[4 * i + c] = w * a.hand_rotations[4 * i + c] + u * a.rotations[4 * i + c];
 }
 
+// One launch of a skinning kernel pair, a workgroup per 256 Gaussians: the sparse instantiation when a->K > 0, else the dense one, each with
+// its bytes of dynamic LDS.  More than 48 KiB of it has to be asked for per kernel; a refusal is this call's error, not the launch's.
+template <class Kernel, class... Rest>
+static int launch_lbs_pair(const AgLbsArgs* a, Kernel sparse_kernel, Kernel dense_kernel, int sparse_lds, int dense_lds, const char* name,
+                           hipStream_t s, Rest... rest)
+{
+    const Kernel kernel = a->K > 0 ? sparse_kernel : dense_kernel;
+    const int lds = a->K > 0 ? sparse_lds : dense_lds;
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) { set_error("%s (LDS size): %s", name, hipGetErrorString(e)); return AG_ERR_HIP; }
+    }
+    hipLaunchKernelGGL(kernel, dim3((a->N + 255) / 256), dim3(256), lds, s, *a, rest...);
+    return check_hip(hipGetLastError(), name);
+}
+
 extern "C" {
 
 int ag_hand_fuse(const AgHandFuseArgs* a, void* stream)
@@ -562,10 +500,16 @@ int ag_hand_fuse(const AgHandFuseArgs* a, void* stream)
     return check_hip(hipGetLastError(), "hand_fuse_kernel");
 }
 
-static int check_gather(const AgGatherArgs* a)
+static int check_gather_sizes(const AgGatherArgs* a)
 {
     if (!a || a->N < 0 || a->S <= 0) { set_error("bad gather sizes"); return AG_ERR_INVALID_ARGUMENT; }
-    if (a->N == 0) return AG_OK;
+    return AG_OK;
+}
+
+static int check_gather(const AgGatherArgs* a)
+{
+    int rc = check_gather_sizes(a);
+    if (rc || a->N == 0) return rc;
     const bool others_all = a->opacity && a->scales && a->rotations, others_none = !a->opacity && !a->scales && !a->rotations;
     if (!a->pix || (a->positions && !a->xyz) || !(others_all || others_none) ||
         (others_all && (!a->opacity_raw || !a->scaling_raw || !a->rotation_raw)) || (!a->positions && others_none && !a->colors)) {
@@ -585,7 +529,8 @@ int ag_gather_activate_forward(const AgGatherArgs* a, void* stream)
 
 int ag_gather_activate_backward(const AgGatherArgs* a, float* g_pos_map, float* g_other_map, float* g_col_map, void* stream)
 {
-    if (!a || a->N < 0 || a->S <= 0) { set_error("bad gather sizes"); return AG_ERR_INVALID_ARGUMENT; }
+    int rc = check_gather_sizes(a);
+    if (rc) return rc;
     if (!g_pos_map && !g_other_map && !g_col_map) { set_error("no gradient map requested"); return AG_ERR_INVALID_ARGUMENT; }
     if (a->N > 0 && (!a->pix || (g_pos_map && !a->positions) || (g_col_map && !a->colors) ||
                      (g_other_map && (!a->other_map || !a->opacity_raw || !a->scaling_raw || !a->rotation_raw || !a->opacity ||
@@ -593,7 +538,6 @@ int ag_gather_activate_backward(const AgGatherArgs* a, float* g_pos_map, float* 
         set_error("AgGatherArgs: a requested gradient map needs its upstream gradients (and, for the other map, the forward inputs)");
         return AG_ERR_INVALID_ARGUMENT;
     }
-    int rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t plane = (size_t)a->S * a->S * sizeof(float);
     if (g_pos_map && (rc = check_hip(hipMemsetAsync(g_pos_map, 0, 6 * plane, s), "memset"))) return rc;
@@ -648,26 +592,12 @@ static int check_lbs(const AgLbsArgs* a)
     return AG_OK;
 }
 
-// Dynamic LDS above 48 KiB has to be asked for per kernel; a refusal is this call's error, not the launch's.
-static int allow_lds(const void* fn, int bytes, const char* what)
-{
-    if (bytes <= 48 * 1024) return AG_OK;
-    return check_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), what);
-}
-
 int ag_lbs_forward(const AgLbsArgs* a, void* stream)
 {
     int rc = check_lbs(a);
     if (rc || a->N == 0) return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (a->K > 0) {
-        hipLaunchKernelGGL(lbs_forward_kernel<true>, dim3((a->N + 255) / 256), dim3(256), 0, s, *a);
-    } else {
-        const int lds = lbs_dense_lds_bytes(a->J);
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&lbs_forward_kernel<false>), lds, "lbs_forward_kernel (LDS size)"))) return rc;
-        hipLaunchKernelGGL(lbs_forward_kernel<false>, dim3((a->N + 255) / 256), dim3(256), lds, s, *a);
-    }
-    return check_hip(hipGetLastError(), "lbs_forward_kernel");
+    return launch_lbs_pair(a, lbs_forward_kernel<true>, lbs_forward_kernel<false>, 0, lbs_dense_lds_bytes(a->J), "lbs_forward_kernel",
+                           reinterpret_cast<hipStream_t>(stream));
 }
 
 int ag_lbs_backward(const AgLbsArgs* a, float* g_positions, float* g_rotations, void* stream)
@@ -675,15 +605,8 @@ int ag_lbs_backward(const AgLbsArgs* a, float* g_positions, float* g_rotations, 
     int rc = check_lbs(a);
     if (rc || a->N == 0) return rc;
     if (!g_positions || !g_rotations) { set_error("null gradient output"); return AG_ERR_INVALID_ARGUMENT; }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (a->K > 0) {
-        hipLaunchKernelGGL(lbs_backward_kernel<true>, dim3((a->N + 255) / 256), dim3(256), 0, s, *a, g_positions, g_rotations);
-    } else {
-        const int lds = lbs_dense_lds_bytes(a->J);
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&lbs_backward_kernel<false>), lds, "lbs_backward_kernel (LDS size)"))) return rc;
-        hipLaunchKernelGGL(lbs_backward_kernel<false>, dim3((a->N + 255) / 256), dim3(256), lds, s, *a, g_positions, g_rotations);
-    }
-    return check_hip(hipGetLastError(), "lbs_backward_kernel");
+    return launch_lbs_pair(a, lbs_backward_kernel<true>, lbs_backward_kernel<false>, 0, lbs_dense_lds_bytes(a->J), "lbs_backward_kernel",
+                           reinterpret_cast<hipStream_t>(stream), g_positions, g_rotations);
 }
 
 size_t ag_lbs_backward_joints_workspace_bytes(int32_t N, int32_t J)
@@ -712,14 +635,8 @@ int ag_lbs_backward_joints(const AgLbsArgs* a, float* g_positions, float* g_rota
         if (!g_positions || !g_rotations) { set_error("lbs_backward_joints: dL_dpositions and dL_drotations are both set or both NULL"); return AG_ERR_INVALID_ARGUMENT; }
         if ((rc = ag_lbs_backward(a, g_positions, g_rotations, stream))) return rc;
     }
-    if (a->K > 0) {
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&lbs_backward_joints_kernel<true>), lds, "lbs_backward_joints_kernel (LDS size)"))) return rc;
-        hipLaunchKernelGGL(lbs_backward_joints_kernel<true>, dim3(nslab), dim3(256), lds, s, *a, slabs);
-    } else {
-        if ((rc = allow_lds(reinterpret_cast<const void*>(&lbs_backward_joints_kernel<false>), lds, "lbs_backward_joints_kernel (LDS size)"))) return rc;
-        hipLaunchKernelGGL(lbs_backward_joints_kernel<false>, dim3(nslab), dim3(256), lds, s, *a, slabs);
-    }
-    if ((rc = check_hip(hipGetLastError(), "lbs_backward_joints_kernel"))) return rc;
+    if ((rc = launch_lbs_pair(a, lbs_backward_joints_kernel<true>, lbs_backward_joints_kernel<false>, lds, lds, "lbs_backward_joints_kernel", s, slabs)))
+        return rc;
     hipLaunchKernelGGL(lbs_joint_slab_reduce_kernel, dim3((a->J * 12 + kSlabOuts - 1) / kSlabOuts), dim3(kSlabOuts * kSlabGroups), 0, s,
                        slabs, nslab, a->J, g_jnt_mats);
     return check_hip(hipGetLastError(), "lbs_joint_slab_reduce_kernel");

@@ -191,6 +191,10 @@ def joints(J, seed, max_shift=0.05):
 LBS_NJ = [(N, J) for J in (55, 64) for N in (1, 63, 64, 65, 255, 256, 257, 1000)] + [(N, J) for J in (1, 2, 24, 140, 160) for N in (65, 257)]
 LBS_SPARSE_ONLY = [("j256_k1", 257, 256, 1), ("j256_k16", 257, 256, 16)]           # sparse only (dense J = 256 does not fit LDS): indices 250..255 in use
 JOINT_GRAD_NJ = [(65, 140), (257, 140)]                                           # the joint gradient at its LDS limit
+# the joint gradient through the shared backward chain: every arg-max candidate and the positive-part branch, a single weight column, one Gaussian beside
+# three idle waves, the product's J with one Gaussian in the second workgroup, J at the edge of one column per lane.  dL/dA is compared over all rows, so
+# none of them may be fragile (tests/test_avatar_kernels_oracle_cpu.py)
+JOINT_GRAD_EDGE = ["branches", "n65_j1", "n1_j55", "n257_j55", "n1000_j64"]
 
 
 def lbs_name(N, J):

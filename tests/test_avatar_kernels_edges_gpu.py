@@ -223,6 +223,20 @@ def test_lbs_joint_gradient_at_its_largest_j(N, J):
     print(f"\n[parity] lbs joint gradient N {N}, J {J}: dL/dA and the four other tensors, dense and sparse (bit-identical): worst ratio to the bar {worst:.3f} (bar 1)")
 
 
+@pytest.mark.parametrize("name", ako.JOINT_GRAD_EDGE)
+def test_lbs_joint_gradient_through_the_shared_chain(name):
+    """dL/dA comes from the routine that also gives dL/drotations (lbs_backward_gaussian of csrc/ag_avatar.hip): here on every arg-max candidate and the
+    positive-part branch of the square root, at J = 1, with one Gaussian beside three idle waves, with one Gaussian in the second workgroup at the product's
+    J, and at J = 64, dense and sparse (bit-identical).  That asking for dL/dA leaves dL/dpositions and dL/drotations the bits of the plain backward is
+    asserted by tests/test_pose_grad_gpu.py::test_lbs_joint_gradient_at_full_size_and_bits."""
+    import torch
+    assert not bool(ako.fragile_rows(name).any()), f"{name}: dL/dA is compared over all rows, none may be fragile"
+    worst, res = _check_lbs(name, joint_grad=True)
+    assert torch.equal(res[4][:, 3], torch.zeros_like(res[4][:, 3])), "row 3 of dL/dA is not exactly 0"
+    d = ako.lbs_case(name)
+    print(f"\n[parity] lbs joint gradient {name}: N {d['N']}, J {d['J']}, dL/dA and the four other tensors, dense and sparse (bit-identical): worst ratio to the bar {worst:.3f} (bar 1)")
+
+
 @pytest.mark.parametrize("form", ["dense", "sparse"])
 def test_lbs_joint_gradient_refuses_j_141(form):
     import torch

@@ -64,7 +64,7 @@ def test_saturated_classes_lie_in_their_logit_range(kind):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # skinning
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ako.all_lbs_cases() + [ako.lbs_name(N, J) for N, J in ako.JOINT_GRAD_NJ if (N, J) not in ako.LBS_NJ])
+@pytest.mark.parametrize("name", list(dict.fromkeys(ako.all_lbs_cases() + [ako.lbs_name(N, J) for N, J in ako.JOINT_GRAD_NJ] + ako.JOINT_GRAD_EDGE)))
 def test_fragile_rows_stay_under_their_cap(name):
     d = ako.lbs_case(name)
     frag = ako.fragile_rows(name)
@@ -74,6 +74,8 @@ def test_fragile_rows_stay_under_their_cap(name):
     assert int(loose.sum()) <= ako.FRAGILE_CAP * d["N"], f"{name}: {int(loose.sum())} fragile rows of {d['N']}"
     if d["N"] <= 1000:
         assert int(loose.sum()) == 0, f"{name}: fragile rows {loose.nonzero().flatten().tolist()} (choose another seed in lbs_case)"
+    if name in ako.JOINT_GRAD_EDGE:                                                   # dL/dA is compared over all rows: none may be fragile at all
+        assert not bool(frag.any()), f"{name}: fragile rows {frag.nonzero().flatten().tolist()}"
 
 
 @pytest.mark.parametrize("name", [n for n in ako.all_lbs_cases() if n not in ("branches", "zero_row")])
