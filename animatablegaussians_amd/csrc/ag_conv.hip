@@ -25,10 +25,15 @@
 // so each lane's 8 operand values of a 32-row block are two ds_read_b128 (8 per wave and tile instead of 32 scalar
 // reads).  Global->register loads of tile k+1 are issued before the MFMAs of tile k and written to the other LDS buffer
 // after them (one LDS-only barrier per K step).
+//
+// Shared routines ("Convolution kernels: what is stated once"): that pipeline is k_loop_split for both split-engine
+// kernels and k_loop_fp32 for gather_conv_kernel; gather_setup is the gather kernels' prologue; wgrad_setup, load_a_quad, gather_b_columns
+// and PixelStepper are wgrad_split_kernel's prologue and scalar loaders; wgrad_kernel keeps its own text for all of these (see there).
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "ag_common.h"
 #include "ag_groups.h"
@@ -100,15 +105,69 @@ __device__ __forceinline__ void mma_half(const Operands<WMB, WNB>& o, int h, f32
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.a[i][h][e], o.b[j][h][e], acc[i][j], 0, 0, 0);
 }
 
-// 32 x 32 x 16 update of a wave's WMB x WNB blocks from the k-contiguous LDS tiles (un-pipelined form, used by wgrad)
 template <int WMB, int WNB>
-__device__ __forceinline__ void mma_tile(const float* __restrict__ As, const float* __restrict__ Bs, int wm, int wn, int lane,
-                                         f32x16 (&acc)[WMB][WNB])
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[WMB][WNB])
 {
-    Operands<WMB, WNB> o;
-    read_operands<WMB, WNB>(As, Bs, wm, wn, lane, o);
-    mma_half<WMB, WNB>(o, 0, acc);
-    mma_half<WMB, WNB>(o, 1, acc);
+#pragma unroll
+    for (int i = 0; i < WMB; i++)
+#pragma unroll
+        for (int j = 0; j < WNB; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+}
+
+// K loop of gather_conv_kernel over the nkt >= 1 K tiles of a workgroup: a three-stage software pipeline.  While the MFMAs of tile k run from operand registers, tile k+1 moves registers -> LDS -> operand registers (one barrier,
+// placed in the middle of the MFMA phase so that the LDS write burst and the operand read burst of all waves are covered by matrix
+// work), and the global loads of tile k+2 are in flight.  Two sets of staging registers (S) and of operand registers (O), declared by the
+// kernel (the form that was measured), alternate by tile parity.  The kernel supplies its loaders: gload(kt, stage) issues the global loads of tile kt (tiles are asked for in ascending
+// order, each once: a loader may keep a running cursor and ignore kt), lstore(buf, stage) writes a loaded tile to LDS buffer buf.
+template <int WMB, int WNB, int BM, int BN, class Stage, class GLoad, class LStore>
+__device__ __forceinline__ void k_loop_fp32(int nkt, const float* As0, const float* Bs0, int wm, int wn, int lane, f32x16 (&acc)[WMB][WNB],
+                                            Stage (&S)[2], Operands<WMB, WNB> (&O)[2], GLoad& gload, LStore& lstore)
+{
+    auto lread = [&](int buf, Operands<WMB, WNB>& o) {
+        read_operands<WMB, WNB>(As0 + buf * BM * LDK, Bs0 + buf * BN * LDK, wm, wn, lane, o);
+    };
+    gload(0, S[0]);
+    if (nkt > 1) gload(1, S[1]);
+    lstore(0, S[0]);
+    lds_barrier();
+    lread(0, O[0]);
+    // Steady-state step for tile kt (kt + 2 < nkt): branch-free, so the compiler's vmcnt bookkeeping stays exact and the
+    // wait before the LDS write covers only the loads issued one step earlier.
+    auto step_full = [&](int kt, Stage& s_same, Stage& s_next, Operands<WMB, WNB>& o_cur, Operands<WMB, WNB>& o_next) {
+        gload(kt + 2, s_same);                                   // s_same held tile kt, already written to LDS
+        mma_half<WMB, WNB>(o_cur, 0, acc);
+        lstore((kt + 1) & 1, s_next);
+        lds_barrier();
+        lread((kt + 1) & 1, o_next);
+        mma_half<WMB, WNB>(o_cur, 1, acc);
+    };
+    auto step_tail = [&](int kt, Stage& s_next, Operands<WMB, WNB>& o_cur, Operands<WMB, WNB>& o_next, bool has_next) {
+        mma_half<WMB, WNB>(o_cur, 0, acc);
+        if (has_next) {
+            lstore((kt + 1) & 1, s_next);
+            lds_barrier();
+            lread((kt + 1) & 1, o_next);
+        }
+        mma_half<WMB, WNB>(o_cur, 1, acc);
+    };
+    int kt = 0;
+    for (; kt + 3 < nkt; kt += 2) {
+        step_full(kt, S[0], S[1], O[0], O[1]);
+        step_full(kt + 1, S[1], S[0], O[1], O[0]);
+    }
+    const int rem = nkt - kt;                                    // 1, 2 or 3 tiles left, kt even
+    if (rem == 3) {
+        step_full(kt, S[0], S[1], O[0], O[1]);
+        step_tail(kt + 1, S[0], O[1], O[0], true);
+        step_tail(kt + 2, S[1], O[0], O[1], false);
+    } else if (rem == 2) {
+        step_tail(kt, S[1], O[0], O[1], true);
+        step_tail(kt + 1, S[0], O[1], O[0], false);
+    } else {
+        step_tail(kt, S[1], O[0], O[1], false);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -290,6 +349,64 @@ __device__ __forceinline__ void gather_epilogue(const GatherProblem& p, const Gr
 // under the MFMAs; spatial padding is applied when the tile is written to LDS.  Nothing in the K loop touches memory for
 // bookkeeping: the per-tap input offsets sit in one VGPR (lane t = tap t) and are fetched with v_readlane; channels past Cg (only
 // the 3- and 12-channel inputs have them) are clamped to the last real channel -- their packed weights are zero.
+//
+// Prologue of both gather kernels: what the workgroup and this loader thread work on, from the class lookup to the K-tile range and the
+// channel cursor.  KG = the consecutive k's of a pixel one thread loads (B loader: NT / BN thread groups).
+struct GatherSetup {
+    const GatherClass* cl;       // class of this workgroup (wave-uniform)
+    GroupView gv;
+    int N, m0, n0;               // pixels of the class; first row and first pixel of the workgroup's tile
+    int n_loc, g;                // this thread's pixel inside the tile and its thread group (wave-uniform: BN >= 64)
+    uint32_t vmask;              // bit t: tap t of the pixel lies inside the image
+    int pix, toff_vec;           // input offset of the pixel; lane t: input offset of tap t (lanes >= ntaps: unused)
+    int ntaps, nkt_all, kt_beg, nkt;   // K tiles of the class, first tile and tile count of this blockIdx.z slice (nkt may be 0 for the short
+                                       // classes of a split launch: zeros are written)
+    // K tile kt = (channel block kt / ntaps, tap kt % ntaps); running (tap, first channel) of the next tile to load
+    int t_cur, c_cur;
+    size_t plane_b;
+    const char* xin_b;
+    int c_last;
+};
+template <int BM, int BN, int KG>
+__device__ __forceinline__ GatherSetup gather_setup(const GatherProblem& p, int tid, int wave, int lane)
+{
+    GatherSetup s;
+    const int bx = blockIdx.x, by = blockIdx.y;
+    int ci = 0;
+#pragma unroll
+    for (int c = 1; c < kMaxClasses; c++)
+        if (c < p.nclasses && bx >= p.cls[c].tile_begin) ci = c;
+    const GatherClass& cl = p.cls[ci];
+    s.cl = &cl;
+    const int gw = cl.gw;
+    s.ntaps = cl.ntaps, s.N = cl.gh * gw;
+    s.gv = group_view(p, by);
+    s.m0 = s.gv.my * BM, s.n0 = (bx - cl.tile_begin) * BN;
+
+    s.n_loc = tid % BN, s.g = (wave * 64) / BN;
+    const int n = s.n0 + s.n_loc;
+    const bool n_ok = n < s.N;
+    const int gy = n_ok ? n / gw : 0, gx = n_ok ? n - (n / gw) * gw : 0;
+    const int iy0 = gy * p.sy, ix0 = gx * p.sx;
+    s.vmask = 0;
+    for (int t = 0; t < s.ntaps; t++) {
+        const int iy = iy0 + cl.dy[t], ix = ix0 + cl.dx[t];
+        if (n_ok && iy >= 0 && iy < p.Hg && ix >= 0 && ix < p.Wg) s.vmask |= 1u << t;
+    }
+    s.pix = iy0 * p.Wg + ix0;
+    const int tl = lane & (kMaxTaps - 1);
+    s.toff_vec = cl.dy[tl] * p.Wg + cl.dx[tl];
+
+    s.nkt_all = cl.nkt;
+    s.kt_beg = min(s.nkt_all, (int)blockIdx.z * p.kt_per_split);
+    s.nkt = min(s.nkt_all, s.kt_beg + p.kt_per_split) - s.kt_beg;
+    s.t_cur = s.kt_beg % s.ntaps;
+    s.c_cur = (s.kt_beg / s.ntaps) * BK + s.g * KG;
+    s.plane_b = (size_t)p.Hg * p.Wg * sizeof(float), s.c_last = p.Cg - 1;
+    s.xin_b = reinterpret_cast<const char*>(s.gv.xin);
+    return s;
+}
+
 template <int WMB, int WNB, int WVM, int WVN>
 __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather_conv_kernel(GatherProblem p)
 {
@@ -304,78 +421,33 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WVN, wn = wave % WVN;
-
-    // class of this workgroup (wave-uniform)
-    const int bx = blockIdx.x, by = blockIdx.y;
-    int ci = 0;
-#pragma unroll
-    for (int c = 1; c < kMaxClasses; c++)
-        if (c < p.nclasses && bx >= p.cls[c].tile_begin) ci = c;
-    const GatherClass& cl = p.cls[ci];
-    const int gw = cl.gw, ntaps = cl.ntaps;
-    const int N = cl.gh * gw;
-    const GroupView gv = group_view(p, by);
-    const int m0 = gv.my * BM, n0 = (bx - cl.tile_begin) * BN;
-
-    const int n_loc = tid % BN, g = (wave * 64) / BN;   // g is wave-uniform (BN >= 64)
-    const int n = n0 + n_loc;
-    const bool n_ok = n < N;
-    const int gy = n_ok ? n / gw : 0, gx = n_ok ? n - (n / gw) * gw : 0;
-    const int iy0 = gy * p.sy, ix0 = gx * p.sx;
-    uint32_t vmask = 0;
-    for (int t = 0; t < ntaps; t++) {
-        const int iy = iy0 + cl.dy[t], ix = ix0 + cl.dx[t];
-        if (n_ok && iy >= 0 && iy < p.Hg && ix >= 0 && ix < p.Wg) vmask |= 1u << t;
-    }
-    const int pix = iy0 * p.Wg + ix0;
-    const int tl = lane & (kMaxTaps - 1);
-    const int toff_vec = cl.dy[tl] * p.Wg + cl.dx[tl];          // lane t: input offset of tap t (lanes >= ntaps: unused)
+    GatherSetup gs = gather_setup<BM, BN, KG>(p, tid, wave, lane);
 
     f32x16 acc[WMB][WNB];
-#pragma unroll
-    for (int i = 0; i < WMB; i++)
-#pragma unroll
-        for (int j = 0; j < WNB; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+    zero_acc<WMB, WNB>(acc);
 
-    const int nkt_all = cl.nkt;
-    const int kt_beg = min(nkt_all, (int)blockIdx.z * p.kt_per_split), kt_end = min(nkt_all, kt_beg + p.kt_per_split);
-    const int nkt = kt_end - kt_beg;                       // may be 0 for the short classes of a split launch: zeros are written
-    // K tile kt = (channel block kt / ntaps, tap kt % ntaps); running (tap, first channel, pointers) of the next tile to load
-    int t_cur = kt_beg % ntaps;
-    int c_cur = (kt_beg / ntaps) * BK + g * KG;
-    const size_t plane_b = (size_t)p.Hg * p.Wg * sizeof(float);
-    const char* const xin_b = reinterpret_cast<const char*>(gv.xin);
-    const int c_last = p.Cg - 1;
-    const char* a_ptr = reinterpret_cast<const char*>(p.At + (size_t)gv.grp * p.at_gs + cl.at_off + ((size_t)gv.my * nkt_all + kt_beg) * (BM * BK));
+    const char* a_ptr = reinterpret_cast<const char*>(p.At + (size_t)gs.gv.grp * p.at_gs + gs.cl->at_off + ((size_t)gs.gv.my * gs.nkt_all + gs.kt_beg) * (BM * BK));
     const uint32_t a_voff = (uint32_t)min(tid, AF - 1) * 16u;       // threads past the tile re-read its last float4
 
-    // Three-stage software pipeline.  While the MFMAs of tile k run from operand registers, tile k+1 moves
-    // registers -> LDS -> operand registers (one barrier, placed in the middle of the MFMA phase so that the LDS write
-    // burst and the operand read burst of all waves are covered by matrix work), and the global loads of tile k+2 are in
-    // flight.  Two sets of staging registers (S) and of operand registers (O) alternate by tile parity.
     struct Stage {
         f32x4 ra;
         float rb[KG];
         bool tap_ok;        // rb[] are real samples for this thread's pixel (else spatial padding -> 0 at the LDS write)
     };
-    Stage S[2];
-    Operands<WMB, WNB> O[2];
     const bool a_thread = tid < AF;
-    auto gload = [&](Stage& st) {
+    auto gload = [&](int, Stage& st) {
         st.ra = *reinterpret_cast<const f32x4*>(a_ptr + a_voff);
         a_ptr += BM * BK * sizeof(float);
-        st.tap_ok = (vmask >> t_cur) & 1u;
-        const int toff = __builtin_amdgcn_readlane(toff_vec, t_cur);
-        const uint32_t voff = st.tap_ok ? (uint32_t)(pix + toff) * 4u : 0u;
+        st.tap_ok = (gs.vmask >> gs.t_cur) & 1u;
+        const int toff = __builtin_amdgcn_readlane(gs.toff_vec, gs.t_cur);
+        const uint32_t voff = st.tap_ok ? (uint32_t)(gs.pix + toff) * 4u : 0u;
 #pragma unroll
         for (int j = 0; j < KG; j++) {
-            const char* src = xin_b + (size_t)min(c_cur + j, c_last) * plane_b;     // uniform
+            const char* src = gs.xin_b + (size_t)min(gs.c_cur + j, gs.c_last) * gs.plane_b;     // uniform
             st.rb[j] = *reinterpret_cast<const float*>(src + voff);
         }
-        t_cur++;
-        if (t_cur == ntaps) { t_cur = 0; c_cur += BK; }
+        gs.t_cur++;
+        if (gs.t_cur == gs.ntaps) { gs.t_cur = 0; gs.c_cur += BK; }
     };
     auto lstore = [&](int buf, const Stage& st) {
         float* As = As0 + buf * BM * LDK;
@@ -386,58 +458,13 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
             f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; e++) v[e] = st.tap_ok ? st.rb[4 * q + e] : 0.f;
-            *reinterpret_cast<f32x4*>(Bs + n_loc * LDK + g * KG + 4 * q) = v;
+            *reinterpret_cast<f32x4*>(Bs + gs.n_loc * LDK + gs.g * KG + 4 * q) = v;
         }
     };
-    auto lread = [&](int buf, Operands<WMB, WNB>& o) {
-        read_operands<WMB, WNB>(As0 + buf * BM * LDK, Bs0 + buf * BN * LDK, wm, wn, lane, o);
-    };
-
-    if (nkt > 0) {
-        gload(S[0]);
-        if (nkt > 1) gload(S[1]);
-        lstore(0, S[0]);
-        lds_barrier();
-        lread(0, O[0]);
-        // Steady-state step for tile kt (kt + 2 < nkt): branch-free, so the compiler's vmcnt bookkeeping stays exact and the
-        // wait before the LDS write covers only the loads issued one step earlier.
-        auto step_full = [&](int kt, Stage& s_same, Stage& s_next, Operands<WMB, WNB>& o_cur, Operands<WMB, WNB>& o_next) {
-            gload(s_same);                                           // s_same held tile kt, already written to LDS
-            mma_half<WMB, WNB>(o_cur, 0, acc);
-            lstore((kt + 1) & 1, s_next);
-            lds_barrier();
-            lread((kt + 1) & 1, o_next);
-            mma_half<WMB, WNB>(o_cur, 1, acc);
-        };
-        auto step_tail = [&](int kt, Stage& s_next, Operands<WMB, WNB>& o_cur, Operands<WMB, WNB>& o_next, bool has_next) {
-            mma_half<WMB, WNB>(o_cur, 0, acc);
-            if (has_next) {
-                lstore((kt + 1) & 1, s_next);
-                lds_barrier();
-                lread((kt + 1) & 1, o_next);
-            }
-            mma_half<WMB, WNB>(o_cur, 1, acc);
-        };
-        int kt = 0;
-        for (; kt + 3 < nkt; kt += 2) {
-            step_full(kt, S[0], S[1], O[0], O[1]);
-            step_full(kt + 1, S[1], S[0], O[1], O[0]);
-        }
-        const int rem = nkt - kt;                                    // 1, 2 or 3 tiles left, kt even
-        if (rem == 3) {
-            step_full(kt, S[0], S[1], O[0], O[1]);
-            step_tail(kt + 1, S[0], O[1], O[0], true);
-            step_tail(kt + 2, S[1], O[0], O[1], false);
-        } else if (rem == 2) {
-            step_tail(kt, S[1], O[0], O[1], true);
-            step_tail(kt + 1, S[0], O[1], O[0], false);
-        } else {
-            step_tail(kt, S[1], O[0], O[1], false);
-        }
-    }
-    // (the gather kernel above and the wgrad kernel below share this loop shape)
-
-    gather_epilogue<WMB, WNB>(p, gv, cl, acc, m0, n0, N, wm, wn, lane);
+    Stage S[2];
+    Operands<WMB, WNB> O[2];
+    if (gs.nkt > 0) k_loop_fp32<WMB, WNB, BM, BN, Stage>(gs.nkt, As0, Bs0, wm, wn, lane, acc, S, O, gload, lstore);
+    gather_epilogue<WMB, WNB>(p, gs.gv, *gs.cl, acc, gs.m0, gs.n0, gs.N, wm, wn, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -498,6 +525,7 @@ constexpr int kF16 = 2;                 // value of the kernels' NTERMS paramete
 // are normal fp16 numbers (|x| >= 2^-29 M); one plane in LDS and in the packed weights, a third of the matrix instructions.
 constexpr int kF16S = 1;
 constexpr bool is_f16_form(int nterms) { return nterms == kF16 || nterms == kF16S; }
+constexpr int planes_of(int nterms) { return nterms == 6 ? 3 : (nterms == kF16S ? 1 : 2); }      // parts per operand that the form stores and reads
 
 __device__ __forceinline__ uint32_t pack_f16(float lo, float hi)        // round to nearest even
 {
@@ -509,6 +537,37 @@ __device__ __forceinline__ void split_pair_h(float y0, float y1, uint32_t& p0, u
     p0 = pack_f16(y0, y1);
     const f16x2 h = __builtin_bit_cast(f16x2, p0);
     p1 = pack_f16(y0 - (float)h[0], y1 - (float)h[1]);
+}
+// one pair of fp32 values -> its words in the planes of the form NTERMS (sc: the tensor's scale, fp16 forms only; the words of planes
+// the form does not store come back as 0)
+template <int NTERMS>
+__device__ __forceinline__ void split_words(float x0, float x1, float sc, uint32_t& a, uint32_t& b, uint32_t& c)
+{
+    b = 0; c = 0;
+    if constexpr (NTERMS == kF16S)        a = pack_f16(x0 * sc, x1 * sc);
+    else if constexpr (is_f16_form(NTERMS)) split_pair_h(x0 * sc, x1 * sc, a, b);
+    else                                  split_pair(x0, x1, a, b, c);
+}
+// the words of one LDS position to the NPL planes (plane_bytes apart) of a tile: V = u32x2, four k's in 8 bytes per plane, or uint32_t, two k's
+template <int NPL, class V>
+__device__ __forceinline__ void store_planes(char* dst, int plane_bytes, V w0, V w1, V w2)
+{
+    *reinterpret_cast<V*>(dst) = w0;
+    if constexpr (NPL >= 2) *reinterpret_cast<V*>(dst + plane_bytes) = w1;
+    if constexpr (NPL == 3) *reinterpret_cast<V*>(dst + 2 * plane_bytes) = w2;
+}
+// four consecutive k's of one row: split and stored, 8 bytes per plane
+template <int NTERMS>
+__device__ __forceinline__ void store_split_quad(char* dst, int plane_bytes, f32x4 v, float sc)
+{
+    u32x2 w0, w1, w2;
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        uint32_t a, b, c;
+        split_words<NTERMS>(v[2 * e], v[2 * e + 1], sc, a, b, c);
+        w0[e] = a; w1[e] = b; w2[e] = c;
+    }
+    store_planes<planes_of(NTERMS)>(dst, plane_bytes, w0, w1, w2);
 }
 // scale of a tensor instance from the partial maxima of absmax_kernel (wave-uniform): s = 2^(14 - e) for a maximum in [2^e, 2^(e+1)),
 // 1 / s exactly; an all-zero (or non-finite) tensor gets s = 1
@@ -608,8 +667,6 @@ __global__ void __launch_bounds__(256) absmax_small_kernel(AmaxJobs J)
 // pitch) on different halves, so the ds_read_b128 of 16 consecutive rows covers all 64 banks once.
 __device__ __forceinline__ int chunk_off(int row, int kh) { return row * kRowB + ((kh ^ ((row >> 3) & 1)) << 4); }
 
-constexpr int planes_of(int nterms) { return nterms == 6 ? 3 : (nterms == kF16S ? 1 : 2); }      // parts per operand that the form stores and reads
-
 template <int WMB, int WNB, int WVM, int WVN, int NPL>
 struct SplitTile {
     static constexpr int BM = 32 * WMB * WVM, BN = 32 * WNB * WVN, NT = 64 * WVM * WVN;
@@ -680,6 +737,61 @@ __device__ __forceinline__ void unscale_f16(f32x16 (&acc)[WMB][WNB], float inv_a
             for (int r = 0; r < 16; r++) acc[i][j][r] = acc[i][j][r] * inv_a * inv_b;
 }
 
+// K-loop driver of the split engine (gather_conv_split_kernel, wgrad_split_kernel) over nkt >= 1 K tiles: k_loop_fp32's pipeline and loader
+// contract (gload(kt, stage), lstore(buf, stage)) with ONE set of operand registers (two would not fit beside the staging registers at 128
+// VGPRs): the LDS reads of tile k are issued right after the barrier, the split + LDS writes of tile k + 1 run under their latency, then the
+// MFMAs.  T: the kernel's SplitTile.  The kernel's scalars arrive by reference and wgrad_setup returns by value on purpose: 24 of these
+// kernels sit at the 128-VGPR cap and the form decides a few bytes of scratch per lane (by-value parameters here: +4 bytes in
+// wgrad_split_kernel<1,2,2,4,*,2,false>; profiles/conv_engine_ab.txt has the table).
+template <class T, int WMB, int WNB, int NTERMS, class Stage, class GLoad, class LStore>
+__device__ __forceinline__ void k_loop_split(const int& nkt, char* const& As0, char* const& Bs0, const int& wm, const int& wn, const int& lane,
+                                             f32x16 (&acc)[WMB][WNB], GLoad& gload, LStore& lstore)
+{
+    Stage S[2];
+    SplitOperands<WMB, WNB> O;
+    auto lread = [&](int buf) {
+        read_split_operands<WMB, WNB, T::BM, T::BN, NTERMS>(As0 + buf * T::a_bytes, Bs0 + buf * T::b_bytes, wm, wn, lane, O);
+    };
+    auto mma = [&]() {
+        if constexpr (is_f16_form(NTERMS)) mma_split_h<WMB, WNB, NTERMS>(O, acc);
+        else                               mma_split<WMB, WNB, NTERMS>(O, acc);
+    };
+    gload(0, S[0]);
+    if (nkt > 1) gload(1, S[1]);
+    lstore(0, S[0]);
+    lds_barrier();
+    // steady state for tile kt (kt + 2 < nkt), branch-free
+    auto step_full = [&](int kt, Stage& s_same, Stage& s_next) {
+        lread(kt & 1);
+        gload(kt + 2, s_same);                 // tile kt + 2 into the registers whose tile (kt) is already in LDS
+        lstore((kt + 1) & 1, s_next);
+        mma();
+        lds_barrier();
+    };
+    auto step_tail = [&](int kt, Stage& s_next, bool has_next) {
+        lread(kt & 1);
+        if (has_next) lstore((kt + 1) & 1, s_next);
+        mma();
+        if (has_next) lds_barrier();
+    };
+    int kt = 0;
+    for (; kt + 3 < nkt; kt += 2) {
+        step_full(kt, S[0], S[1]);
+        step_full(kt + 1, S[1], S[0]);
+    }
+    const int rem = nkt - kt;                  // 1, 2 or 3 tiles left, kt even
+    if (rem == 3) {
+        step_full(kt, S[0], S[1]);
+        step_tail(kt + 1, S[0], true);
+        step_tail(kt + 2, S[1], false);
+    } else if (rem == 2) {
+        step_tail(kt, S[1], true);
+        step_tail(kt + 1, S[0], false);
+    } else {
+        step_tail(kt, S[1], false);
+    }
+}
+
 // gather_conv_kernel on the split engine.  Same K order, same classes, same epilogue; differences: the packed weights arrive already
 // split (pack_weights_split_kernel: per K tile three planes [BM][16] bf16, chunks pre-swizzled, so the loader copies 16-byte chunks
 // straight through), the gathered activations are split by the loader thread between the global load and the LDS write, and one set
@@ -708,54 +820,17 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WVN, wn = wave % WVN;
-
-    const int bx = blockIdx.x, by = blockIdx.y;
-    int ci = 0;
-#pragma unroll
-    for (int c = 1; c < kMaxClasses; c++)
-        if (c < p.nclasses && bx >= p.cls[c].tile_begin) ci = c;
-    const GatherClass& cl = p.cls[ci];
-    const int gw = cl.gw, ntaps = cl.ntaps;
-    const int N = cl.gh * gw;
-    const GroupView gv = group_view(p, by);
-    const int m0 = gv.my * BM, n0 = (bx - cl.tile_begin) * BN;
-
-    const int n_loc = tid % BN, g = (wave * 64) / BN;
-    const int n = n0 + n_loc;
-    const bool n_ok = n < N;
-    const int gy = n_ok ? n / gw : 0, gx = n_ok ? n - (n / gw) * gw : 0;
-    const int iy0 = gy * p.sy, ix0 = gx * p.sx;
-    uint32_t vmask = 0;
-    for (int t = 0; t < ntaps; t++) {
-        const int iy = iy0 + cl.dy[t], ix = ix0 + cl.dx[t];
-        if (n_ok && iy >= 0 && iy < p.Hg && ix >= 0 && ix < p.Wg) vmask |= 1u << t;
-    }
-    const int pix = iy0 * p.Wg + ix0;
-    const int tl = lane & (kMaxTaps - 1);
-    const int toff_vec = cl.dy[tl] * p.Wg + cl.dx[tl];
+    GatherSetup gs = gather_setup<BM, BN, KG>(p, tid, wave, lane);
 
     f32x16 acc[WMB][WNB];
-#pragma unroll
-    for (int i = 0; i < WMB; i++)
-#pragma unroll
-        for (int j = 0; j < WNB; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+    zero_acc<WMB, WNB>(acc);
 
-    const int nkt_all = cl.nkt;
-    const int kt_beg = min(nkt_all, (int)blockIdx.z * p.kt_per_split), kt_end = min(nkt_all, kt_beg + p.kt_per_split);
-    const int nkt = kt_end - kt_beg;
-    int t_cur = kt_beg % ntaps;
-    int c_cur = (kt_beg / ntaps) * BK + g * KG;
-    const size_t plane_b = (size_t)p.Hg * p.Wg * sizeof(float);
-    const char* const xin_b = reinterpret_cast<const char*>(gv.xin);
-    const int c_last = p.Cg - 1;
     // packed weights: cl.at_off counts fp32-tile floats (BM * 16 per tile); a split tile has a_bytes = 2 bytes per element and plane
-    const char* a_ptr = reinterpret_cast<const char*>(p.At) + ((size_t)gv.grp * p.at_gs + (size_t)cl.at_off) * (2 * NPL) + ((size_t)gv.my * nkt_all + kt_beg) * T::a_bytes;
+    const char* a_ptr = reinterpret_cast<const char*>(p.At) + ((size_t)gs.gv.grp * p.at_gs + (size_t)gs.cl->at_off) * (2 * NPL) + ((size_t)gs.gv.my * gs.nkt_all + gs.kt_beg) * T::a_bytes;
     TensorScale sa{ 1.f, 1.f }, sb{ 1.f, 1.f };
     if constexpr (F16) {
-        sa = tensor_scale(p.amax_a + (size_t)gv.grp * kAmaxParts, p.amax_a_mult, lane);
-        sb = tensor_scale(p.amax_b + (p.x_gs ? (size_t)gv.grp * kAmaxParts : 0), 1.f, lane);
+        sa = tensor_scale(p.amax_a + (size_t)gs.gv.grp * kAmaxParts, p.amax_a_mult, lane);
+        sb = tensor_scale(p.amax_b + (p.x_gs ? (size_t)gs.gv.grp * kAmaxParts : 0), 1.f, lane);
     }
 
     const uint32_t a_voff0 = (uint32_t)min(tid, AC - 1) * 16u;
@@ -763,15 +838,15 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
     const bool a_thread0 = tid < AC;                  // wave-uniform (AC is a multiple of 64)
     const bool a_thread1 = A2 && NT + tid < AC;
     // LDS write position of this thread's KG values: row n_loc, k = g * KG ...
-    const int b_woff = chunk_off(n_loc, (g * KG) >> 3) + ((g * KG) & 7) * 2;
+    const int b_woff = chunk_off(gs.n_loc, (gs.g * KG) >> 3) + ((gs.g * KG) & 7) * 2;
 
     // uniform base pointers of the KG channel planes of the current channel block (scalar registers; refreshed once per block)
     const char* cbase[KG];
     uint32_t cb_off = 0;                              // CEXACT: byte offset of the current channel block (host checks the tensor < 4 GB)
-    const uint32_t cb_step = (uint32_t)(BK * plane_b);
+    const uint32_t cb_step = (uint32_t)(BK * gs.plane_b);
     auto set_bases = [&]() {
 #pragma unroll
-        for (int j = 0; j < KG; j++) cbase[j] = xin_b + (size_t)min(c_cur + j, c_last) * plane_b;
+        for (int j = 0; j < KG; j++) cbase[j] = gs.xin_b + (size_t)min(gs.c_cur + j, gs.c_last) * gs.plane_b;
     };
     set_bases();
 
@@ -780,26 +855,24 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
         float rb[KG];
         bool tap_ok;
     };
-    Stage S[2];
-    SplitOperands<WMB, WNB> O;
-    auto gload = [&](Stage& st) {
+    auto gload = [&](int, Stage& st) {
         st.ra0 = *reinterpret_cast<const u32x4*>(a_ptr + a_voff0);
         if constexpr (A2) st.ra1 = *reinterpret_cast<const u32x4*>(a_ptr + a_voff1);
         a_ptr += T::a_bytes;
-        st.tap_ok = (vmask >> t_cur) & 1u;
-        const int toff = __builtin_amdgcn_readlane(toff_vec, t_cur);
-        const uint32_t voff = st.tap_ok ? (uint32_t)(pix + toff) * 4u + (CEXACT ? cb_off : 0u) : 0u;
+        st.tap_ok = (gs.vmask >> gs.t_cur) & 1u;
+        const int toff = __builtin_amdgcn_readlane(gs.toff_vec, gs.t_cur);
+        const uint32_t voff = st.tap_ok ? (uint32_t)(gs.pix + toff) * 4u + (CEXACT ? cb_off : 0u) : 0u;
 #pragma unroll
         for (int j = 0; j < KG; j++) {
             st.rb[j] = *reinterpret_cast<const float*>(cbase[j] + voff);     // global_load_dword v, v_off, s[base]
         }
-        t_cur++;
+        gs.t_cur++;
         if constexpr (CEXACT) {
-            const bool wrap = t_cur == ntaps;
-            t_cur = wrap ? 0 : t_cur;
+            const bool wrap = gs.t_cur == gs.ntaps;
+            gs.t_cur = wrap ? 0 : gs.t_cur;
             cb_off += wrap ? cb_step : 0u;
         } else {
-            if (t_cur == ntaps) { t_cur = 0; c_cur += BK; set_bases(); }
+            if (gs.t_cur == gs.ntaps) { gs.t_cur = 0; gs.c_cur += BK; set_bases(); }
         }
     };
     auto lstore = [&](int buf, const Stage& st) {
@@ -811,67 +884,15 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) gather
         }
 #pragma unroll
         for (int q = 0; q < KG / 4; q++) {
-            u32x2 w0, w1, w2;
+            f32x4 v;
 #pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const float x0 = st.tap_ok ? st.rb[4 * q + 2 * e] : 0.f, x1 = st.tap_ok ? st.rb[4 * q + 2 * e + 1] : 0.f;
-                uint32_t a, b = 0, c = 0;
-                if constexpr (NTERMS == kF16S) a = pack_f16(x0 * sb.s, x1 * sb.s);
-                else if constexpr (F16)        split_pair_h(x0 * sb.s, x1 * sb.s, a, b);
-                else                           split_pair(x0, x1, a, b, c);
-                w0[e] = a; w1[e] = b; w2[e] = c;
-            }
-            *reinterpret_cast<u32x2*>(Bs + 0 * BN * kRowB + b_woff + 8 * q) = w0;
-            if constexpr (NPL >= 2) *reinterpret_cast<u32x2*>(Bs + 1 * BN * kRowB + b_woff + 8 * q) = w1;
-            if constexpr (NPL == 3) *reinterpret_cast<u32x2*>(Bs + 2 * BN * kRowB + b_woff + 8 * q) = w2;
+            for (int e = 0; e < 4; e++) v[e] = st.tap_ok ? st.rb[4 * q + e] : 0.f;
+            store_split_quad<NTERMS>(Bs + b_woff + 8 * q, BN * kRowB, v, sb.s);
         }
     };
-    auto lread = [&](int buf) {
-        read_split_operands<WMB, WNB, BM, BN, NTERMS>(As0 + buf * T::a_bytes, Bs0 + buf * T::b_bytes, wm, wn, lane, O);
-    };
-    auto mma = [&]() {
-        if constexpr (F16) mma_split_h<WMB, WNB, NTERMS>(O, acc);
-        else               mma_split<WMB, WNB, NTERMS>(O, acc);
-    };
-
-    if (nkt > 0) {
-        gload(S[0]);
-        if (nkt > 1) gload(S[1]);
-        lstore(0, S[0]);
-        lds_barrier();
-        // steady state for tile kt (kt + 2 < nkt), branch-free
-        auto step_full = [&](int kt, Stage& s_same, Stage& s_next) {
-            lread(kt & 1);
-            gload(s_same);                         // tile kt + 2 into the registers whose tile (kt) is already in LDS
-            lstore((kt + 1) & 1, s_next);
-            mma();
-            lds_barrier();
-        };
-        auto step_tail = [&](int kt, Stage& s_next, bool has_next) {
-            lread(kt & 1);
-            if (has_next) lstore((kt + 1) & 1, s_next);
-            mma();
-            if (has_next) lds_barrier();
-        };
-        int kt = 0;
-        for (; kt + 3 < nkt; kt += 2) {
-            step_full(kt, S[0], S[1]);
-            step_full(kt + 1, S[1], S[0]);
-        }
-        const int rem = nkt - kt;
-        if (rem == 3) {
-            step_full(kt, S[0], S[1]);
-            step_tail(kt + 1, S[0], true);
-            step_tail(kt + 2, S[1], false);
-        } else if (rem == 2) {
-            step_tail(kt, S[1], true);
-            step_tail(kt + 1, S[0], false);
-        } else {
-            step_tail(kt, S[1], false);
-        }
-    }
+    if (gs.nkt > 0) k_loop_split<T, WMB, WNB, NTERMS, Stage>(gs.nkt, As0, Bs0, wm, wn, lane, acc, gload, lstore);
     if constexpr (F16) unscale_f16<WMB, WNB>(acc, sa.inv, sb.inv);
-    gather_epilogue<WMB, WNB>(p, gv, cl, acc, m0, n0, N, wm, wn, lane);
+    gather_epilogue<WMB, WNB>(p, gs.gv, *gs.cl, acc, gs.m0, gs.n0, gs.N, wm, wn, lane);
 }
 
 // split-K finish: y = (sum_z partial[z][m][col]) * out_scale[m] + bias[m], in a fixed order (deterministic)
@@ -1181,6 +1202,114 @@ __global__ void __launch_bounds__(256) wgrad_reduce_par_kernel(WgradReduce r)
 // AVEC: the rows of A are 16-byte aligned (pixel count a multiple of 4, always true in the product): one dwordx4 per thread and
 // tile; the scalar form is kept for arbitrary sizes.  Everything in the K loop is branch-free: loads are unconditional from clamped
 // addresses, validity (image border, end of the K slice) travels as a bit mask and is applied at the LDS write.
+//
+// Prologue and scalar loaders of wgrad_split_kernel: what the workgroup works on (instance, tile, pixel slice) and the loaders' per-thread state.  A loader: row am, 4 consecutive pixels aq .. aq + 3 (A is pixel-contiguous).  B loader: pixel bk of the tile
+// (lanes run along pixels), columns bn, bn + BSTEP, ...; a column = (channel, tap) is fixed per thread for the whole kernel: its plane +
+// tap offset and its tap displacement live in registers.
+template <int BM, int BN, int NT>
+struct WgradSetup {
+    static constexpr int BSTEP = NT / 16;              // B loader: columns covered per pass
+    static constexpr int BC = BN / BSTEP;              // columns per thread
+    int Kp, Nw, grp, m0, n0, kbeg, kend;
+    const float* xin_g;
+    float* c_g;
+    int am, aq;
+    bool a_thread;
+    const float* a_row;
+    int bk, bn;
+    int col_off[BC], col_dy[BC], col_dx[BC];
+};
+// A thread's pixel of the NEXT tile to load, advanced by BK pixels per tile without a division or a loop: BK = qstep * gw + rstep with
+// rstep < gw, so one conditional wrap is exact for every grid width
+struct PixelStepper {
+    int kpix, gy, gx, qstep, rstep;
+    __device__ __forceinline__ PixelStepper(int first, int gw)
+    {
+        kpix = first;
+        gy = kpix / gw, gx = kpix - gy * gw;
+        qstep = BK / gw, rstep = BK - qstep * gw;
+    }
+    __device__ __forceinline__ void advance(int gw)
+    {
+        kpix += BK;
+        gx += rstep;
+        gy += qstep;
+        const bool wrap = gx >= gw;
+        gx -= wrap ? gw : 0;
+        gy += wrap ? 1 : 0;
+    }
+};
+// An empty pixel slice (kbeg >= kend) returns early with the per-thread fields unset: the caller tests for it and leaves the kernel.
+template <int BM, int BN, int NT>
+__device__ __forceinline__ WgradSetup<BM, BN, NT> wgrad_setup(const WgradProblem& p, int tid)
+{
+    using W = WgradSetup<BM, BN, NT>;
+    W w;
+    static_assert(BM * 4 <= NT, "A loader: one row quarter per thread");
+    w.Kp = p.gh * p.gw, w.Nw = p.Cg * p.ntaps;
+    w.grp = (int)blockIdx.y / p.mtiles;                                     // grouped launch (ag_groups.h)
+    const int my = (int)blockIdx.y - w.grp * p.mtiles;
+    w.xin_g = p.xin + (size_t)w.grp * p.xin_gs;
+    w.c_g = p.c_t.p[0] ? const_cast<float*>(p.c_t.p[w.grp]) : p.c + (size_t)w.grp * p.c_gs;
+    w.m0 = my * BM, w.n0 = blockIdx.x * BN;
+    w.kbeg = blockIdx.z * p.ksplit_len, w.kend = min(w.Kp, w.kbeg + p.ksplit_len);
+    if (w.kbeg >= w.kend) return w;
+
+    w.am = tid >> 2, w.aq = (tid & 3) * 4;
+    w.a_thread = w.am < BM && (w.m0 + w.am) < p.Mw;
+    w.a_row = p.a + (size_t)w.grp * p.a_gs + (size_t)min(w.m0 + w.am, p.Mw - 1) * w.Kp;
+    w.bk = tid & 15, w.bn = tid >> 4;
+    const int plane = p.Hg * p.Wg;
+#pragma unroll
+    for (int j = 0; j < W::BC; j++) {
+        const int nn = w.n0 + w.bn + W::BSTEP * j;
+        const int c = min(nn / p.ntaps, p.Cg - 1), t = nn % p.ntaps;
+        w.col_dy[j] = (nn < w.Nw) ? p.dy[t] : (1 << 28);               // out-of-range columns fail the bounds test below
+        w.col_dx[j] = p.dx[t];
+        w.col_off[j] = c * plane + p.dy[t] * p.Wg + p.dx[t];
+    }
+    return w;
+}
+// A quad of the tile that starts at pixel k0 -> ra; returns whether it is real (else zero at the LDS write).  AVEC: one dwordx4 load --
+// every 4-group lies entirely inside or outside [kbeg, kend)
+template <bool AVEC, class W>
+__device__ __forceinline__ bool load_a_quad(const W& w, int k0, f32x4& ra)
+{
+    const int ka = k0 + w.aq;
+    const bool a_ok = w.a_thread && ka < w.kend;
+    if constexpr (AVEC) {
+        ra = *reinterpret_cast<const f32x4*>(w.a_row + (a_ok ? ka : 0));
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const bool in = a_ok && ka + q < w.kend;
+            const float v = w.a_row[in ? ka + q : 0];
+            ra[q] = in ? v : 0.f;
+        }
+    }
+    return a_ok;
+}
+// scalar B gather of the stepper's pixel: one value per column into rb, bit j of the result = rb[j] is a real sample; then the stepper
+// moves to the next tile
+template <class W>
+__device__ __forceinline__ uint32_t gather_b_columns(const WgradProblem& p, const W& w, PixelStepper& px, float (&rb)[W::BC])
+{
+    uint32_t ok = 0;
+    const bool k_ok = px.kpix < w.kend;
+    const int iy0 = px.gy * p.sy, ix0 = px.gx * p.sx;
+    const int pixoff = iy0 * p.Wg + ix0;
+#pragma unroll
+    for (int j = 0; j < W::BC; j++) {
+        const bool in = k_ok & ((unsigned)(iy0 + w.col_dy[j]) < (unsigned)p.Hg) & ((unsigned)(ix0 + w.col_dx[j]) < (unsigned)p.Wg);
+        rb[j] = w.xin_g[in ? w.col_off[j] + pixoff : 0];
+        ok |= in ? (1u << j) : 0u;
+    }
+    px.advance(p.gw);
+    return ok;
+}
+
+// wgrad_kernel states its prologue, scalar loaders and K loop itself: through wgrad_setup and its loaders, or through k_loop_fp32, it measured
+// 1 to 2 % slower (profiles/conv_engine_ab.txt, "Which routine").  A change to the pipeline or to the scalar loaders belongs here too.
 template <int WMB, int WNB, int WVM, int WVN, bool AVEC>
 __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_kernel(WgradProblem p)
 {
@@ -1207,8 +1336,6 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_
     const int am = tid >> 2, aq = (tid & 3) * 4;
     const bool a_thread = am < BM && (m0 + am) < p.Mw;
     const float* a_row = p.a + (size_t)grp * p.a_gs + (size_t)min(m0 + am, p.Mw - 1) * Kp;
-    // B loader: pixel bk of the tile (lanes run along pixels), columns bn, bn + BSTEP, ...; a column = (channel, tap) is fixed per
-    // thread for the whole kernel: its plane + tap offset and its tap displacement live in registers
     const int bk = tid & 15, bn = tid >> 4;
     const int plane = p.Hg * p.Wg;
     int col_off[BC], col_dy[BC], col_dx[BC];
@@ -1220,8 +1347,6 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_
         col_dx[j] = p.dx[t];
         col_off[j] = c * plane + p.dy[t] * p.Wg + p.dx[t];
     }
-    // this thread's pixel of the NEXT tile to load, advanced by BK pixels per tile without a division or a loop:
-    // BK = qstep * gw + rstep with rstep < gw, so one conditional wrap is exact for every grid width
     int kpix = kbeg + bk;
     int gy = kpix / p.gw, gx = kpix - gy * p.gw;
     const int qstep = BK / p.gw, rstep = BK - qstep * p.gw;
@@ -1287,7 +1412,6 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_
         read_operands<WMB, WNB>(As0 + buf * BM * LDK, Bs0 + buf * BN * LDK, wm, wn, lane, o);
     };
 
-    // same three-stage pipeline as gather_conv_kernel
     const int nkt = (kend - kbeg + BK - 1) / BK;
     gload(kbeg, S[0]);
     if (nkt > 1) gload(kbeg + BK, S[1]);
@@ -1350,86 +1474,54 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_
     constexpr bool F16 = is_f16_form(NTERMS);
     using T = SplitTile<WMB, WNB, WVM, WVN, NPL>;
     constexpr int BM = T::BM, BN = T::BN, NT = T::NT;
-    constexpr int BSTEP = NT / 16;
-    constexpr int BC = BN / BSTEP;
+    using W = WgradSetup<BM, BN, NT>;
+    constexpr int BSTEP = W::BSTEP, BC = W::BC;
     constexpr int BCV = BN / (NT / 4);                 // BVEC: columns per thread (a thread = 4 consecutive k of a column)
-    static_assert(BM * 4 <= NT && BC % 2 == 0 && BCV >= 1, "loader shapes");
+    static_assert(BC % 2 == 0 && BCV >= 1, "loader shapes");
     __shared__ __attribute__((aligned(16))) char smem[T::lds_bytes];
     char* const As0 = smem;
     char* const Bs0 = smem + 2 * T::a_bytes;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WVN, wn = wave % WVN;
-    const int Kp = p.gh * p.gw, Nw = p.Cg * p.ntaps;
-    const int grp = (int)blockIdx.y / p.mtiles, my = (int)blockIdx.y - grp * p.mtiles;      // grouped launch (ag_groups.h)
-    const float* __restrict__ xin_g = p.xin + (size_t)grp * p.xin_gs;
-    float* __restrict__ c_g = p.c_t.p[0] ? const_cast<float*>(p.c_t.p[grp]) : p.c + (size_t)grp * p.c_gs;
-    const int m0 = my * BM, n0 = blockIdx.x * BN;
-    const int kbeg = blockIdx.z * p.ksplit_len, kend = min(Kp, kbeg + p.ksplit_len);
-    if (kbeg >= kend) return;
+    W w = wgrad_setup<BM, BN, NT>(p, tid);
+    if (w.kbeg >= w.kend) return;
 
-    const int am = tid >> 2, aq = (tid & 3) * 4;
-    const bool a_thread = am < BM && (m0 + am) < p.Mw;
-    const float* a_row = p.a + (size_t)grp * p.a_gs + (size_t)min(m0 + am, p.Mw - 1) * Kp;
-    const int a_woff = chunk_off(min(am, BM - 1), aq >> 3) + (aq & 7) * 2;
-    const int bk = tid & 15, bn = tid >> 4;
-    const int plane = p.Hg * p.Wg;
-    int col_off[BC], col_dy[BC], col_dx[BC];
-#pragma unroll
-    for (int j = 0; j < BC; j++) {
-        const int nn = n0 + bn + BSTEP * j;
-        const int c = min(nn / p.ntaps, p.Cg - 1), t = nn % p.ntaps;
-        col_dy[j] = (nn < Nw) ? p.dy[t] : (1 << 28);
-        col_dx[j] = p.dx[t];
-        col_off[j] = c * plane + p.dy[t] * p.Wg + p.dx[t];
-    }
+    const int a_woff = chunk_off(min(w.am, BM - 1), w.aq >> 3) + (w.aq & 7) * 2;
     // after the pair swap an even lane writes pixels (bk, bk + 1) of the first column of each pair, an odd lane pixels (bk - 1, bk) of
     // the second: LDS word of row (bn + BSTEP * j), k = bk & ~1
-    const int odd = bk & 1;
+    const int odd = w.bk & 1;
     int b_woff[BC / 2];
 #pragma unroll
     for (int h = 0; h < BC / 2; h++) {
-        const int row = bn + BSTEP * (2 * h + odd), k = bk & ~1;
+        const int row = w.bn + BSTEP * (2 * h + odd), k = w.bk & ~1;
         b_woff[h] = chunk_off(row, k >> 3) + (k & 7) * 2;
     }
-    int kpix = kbeg + bk;
-    int gy = kpix / p.gw, gx = kpix - gy * p.gw;
-    const int qstep = BK / p.gw, rstep = BK - qstep * p.gw;
+    PixelStepper px(w.kbeg + w.bk, p.gw);
     // BVEC state: this thread's k quad, its columns' channel base / tap displacement, LDS word, and the tile's first pixel (row gy0, column gx0)
     const int vq = tid & 3, vn = tid >> 2;
     int vcol_base[BCV], vcol_dy[BCV], vcol_dx[BCV], vb_woff[BCV];
     if constexpr (BVEC) {
+        const int plane = p.Hg * p.Wg;
 #pragma unroll
         for (int j = 0; j < BCV; j++) {
-            const int nn = n0 + vn + (NT / 4) * j;
+            const int nn = w.n0 + vn + (NT / 4) * j;
             const int c = min(nn / p.ntaps, p.Cg - 1), t = nn % p.ntaps;
-            vcol_dy[j] = (nn < Nw) ? p.dy[t] : (1 << 28);
+            vcol_dy[j] = (nn < w.Nw) ? p.dy[t] : (1 << 28);
             vcol_dx[j] = p.dx[t];
             vcol_base[j] = c * plane;
             vb_woff[j] = chunk_off(vn + (NT / 4) * j, (4 * vq) >> 3) + ((4 * vq) & 7) * 2;
         }
     }
-    int gy0 = kbeg / p.gw, gx0 = kbeg - gy0 * p.gw;
+    int gy0 = w.kbeg / p.gw, gx0 = w.kbeg - gy0 * p.gw;
 
     f32x16 acc[WMB][WNB];
-#pragma unroll
-    for (int i = 0; i < WMB; i++)
-#pragma unroll
-        for (int j = 0; j < WNB; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+    zero_acc<WMB, WNB>(acc);
     TensorScale sa{ 1.f, 1.f }, sb{ 1.f, 1.f };
     if constexpr (F16) {
-        sa = tensor_scale(p.amax_a + (p.a_gs ? (size_t)grp * kAmaxParts : 0), 1.f, lane);
-        sb = tensor_scale(p.amax_b + (p.xin_gs ? (size_t)grp * kAmaxParts : 0), 1.f, lane);
+        sa = tensor_scale(p.amax_a + (p.a_gs ? (size_t)w.grp * kAmaxParts : 0), 1.f, lane);
+        sb = tensor_scale(p.amax_b + (p.xin_gs ? (size_t)w.grp * kAmaxParts : 0), 1.f, lane);
     }
-    // one pair of fp32 values -> its words in the planes (w2 unused by the two-plane forms)
-    auto split2 = [&](float x0, float x1, float sc, uint32_t& a, uint32_t& b, uint32_t& c) {
-        b = 0; c = 0;
-        if constexpr (NTERMS == kF16S) a = pack_f16(x0 * sc, x1 * sc);
-        else if constexpr (F16)        split_pair_h(x0 * sc, x1 * sc, a, b);
-        else                           split_pair(x0, x1, a, b, c);
-    };
 
     struct Stage {
         f32x4 ra;
@@ -1437,22 +1529,8 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_
         f32x4 rv[BVEC ? BCV : 1];
         uint32_t ok;           // bit 31: the A quad is real; scalar form: bit j = column j's value is real; BVEC: 2 bits per column (row ok, edge code)
     };
-    Stage S[2];
-    SplitOperands<WMB, WNB> O;
-    auto gload = [&](int k0, Stage& st) {
-        const int ka = k0 + aq;
-        const bool a_ok = a_thread && ka < kend;
-        if constexpr (AVEC) {
-            st.ra = *reinterpret_cast<const f32x4*>(a_row + (a_ok ? ka : 0));
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const bool in = a_ok && ka + q < kend;
-                const float v = a_row[in ? ka + q : 0];
-                st.ra[q] = in ? v : 0.f;
-            }
-        }
-        uint32_t ok = a_ok ? 0x80000000u : 0u;
+    auto gload = [&](int kt, Stage& st) {
+        uint32_t ok = load_a_quad<AVEC>(w, w.kbeg + kt * BK, st.ra) ? 0x80000000u : 0u;
         if constexpr (BVEC) {
             // whole tiles only (host: pixel count and slice length are multiples of 16): row gy0, columns gx0 .. gx0 + 15
             const int x0 = gx0 + 4 * vq;
@@ -1462,49 +1540,25 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_
                 const bool row_ok = (unsigned)iy < (unsigned)p.Hg;
                 const int edge = ix < 0 ? 1 : (ix + 4 > p.Wg ? 2 : 0);           // the quad sticks out by one element on the left / right
                 const int lx = ix + (edge == 1 ? 1 : 0) - (edge == 2 ? 1 : 0);
-                st.rv[j] = *reinterpret_cast<const f32x4*>(xin_g + vcol_base[j] + (row_ok ? iy : gy0) * p.Wg + lx);
+                st.rv[j] = *reinterpret_cast<const f32x4*>(w.xin_g + vcol_base[j] + (row_ok ? iy : gy0) * p.Wg + lx);
                 ok |= ((row_ok ? 1u : 0u) | ((uint32_t)edge << 1)) << (3 * j);
             }
-            st.ok = ok;
             gx0 += BK;
             const bool wrap0 = gx0 >= p.gw;
             gx0 -= wrap0 ? p.gw : 0;
             gy0 += wrap0 ? 1 : 0;
-            return;
-        }
-        const bool k_ok = kpix < kend;
-        const int iy0 = gy * p.sy, ix0 = gx * p.sx;
-        const int pixoff = iy0 * p.Wg + ix0;
-#pragma unroll
-        for (int j = 0; j < BC; j++) {
-            const bool in = k_ok & ((unsigned)(iy0 + col_dy[j]) < (unsigned)p.Hg) & ((unsigned)(ix0 + col_dx[j]) < (unsigned)p.Wg);
-            st.rb[j] = xin_g[in ? col_off[j] + pixoff : 0];
-            ok |= in ? (1u << j) : 0u;
+        } else {
+            ok |= gather_b_columns(p, w, px, st.rb);
         }
         st.ok = ok;
-        kpix += BK;
-        gx += rstep;
-        gy += qstep;
-        const bool wrap = gx >= p.gw;
-        gx -= wrap ? p.gw : 0;
-        gy += wrap ? 1 : 0;
     };
     auto lstore = [&](int buf, const Stage& st) {
         char* As = As0 + buf * T::a_bytes;
         char* Bs = Bs0 + buf * T::b_bytes;
-        if (am < BM) {
+        if (w.am < BM) {
             f32x4 v = st.ra;
             if (!(st.ok >> 31)) v = f32x4{ 0.f, 0.f, 0.f, 0.f };
-            u32x2 w0, w1, w2;
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                uint32_t a, b, c;
-                split2(v[2 * e], v[2 * e + 1], sa.s, a, b, c);
-                w0[e] = a; w1[e] = b; w2[e] = c;
-            }
-            *reinterpret_cast<u32x2*>(As + 0 * BM * kRowB + a_woff) = w0;
-            if constexpr (NPL >= 2) *reinterpret_cast<u32x2*>(As + 1 * BM * kRowB + a_woff) = w1;
-            if constexpr (NPL == 3) *reinterpret_cast<u32x2*>(As + 2 * BM * kRowB + a_woff) = w2;
+            store_split_quad<NTERMS>(As + a_woff, BM * kRowB, v, sa.s);
         }
         if constexpr (BVEC) {
 #pragma unroll
@@ -1515,77 +1569,23 @@ __global__ void __launch_bounds__(64 * WVM * WVN, AG_CONV_WAVES_PER_SIMD) wgrad_
                 if (f & 2u) v = f32x4{ 0.f, L[0], L[1], L[2] };           // left edge: loaded un-shifted, element -1 is padding
                 if (f & 4u) v = f32x4{ L[1], L[2], L[3], 0.f };           // right edge
                 if (!(f & 1u)) v = f32x4{ 0.f, 0.f, 0.f, 0.f };           // row outside the image (or a column past the last one)
-                u32x2 w0, w1, w2;
-#pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    uint32_t a, b, c;
-                    split2(v[2 * e], v[2 * e + 1], sb.s, a, b, c);
-                    w0[e] = a; w1[e] = b; w2[e] = c;
-                }
-                *reinterpret_cast<u32x2*>(Bs + 0 * BN * kRowB + vb_woff[j]) = w0;
-                if constexpr (NPL >= 2) *reinterpret_cast<u32x2*>(Bs + 1 * BN * kRowB + vb_woff[j]) = w1;
-                if constexpr (NPL == 3) *reinterpret_cast<u32x2*>(Bs + 2 * BN * kRowB + vb_woff[j]) = w2;
+                store_split_quad<NTERMS>(Bs + vb_woff[j], BN * kRowB, v, sb.s);
             }
-            return;
-        }
+        } else {
 #pragma unroll
-        for (int h = 0; h < BC / 2; h++) {
-            const float v0 = ((st.ok >> (2 * h)) & 1u) ? st.rb[2 * h] : 0.f, v1 = ((st.ok >> (2 * h + 1)) & 1u) ? st.rb[2 * h + 1] : 0.f;
-            // even lane gives away its second-column value and keeps the first; odd lane the other way round
-            const float give = odd ? v0 : v1, keep = odd ? v1 : v0;
-            const float got = __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(give), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-            uint32_t a, b, c;
-            split2(odd ? got : keep, odd ? keep : got, sb.s, a, b, c);        // (pixel k & ~1, pixel (k & ~1) + 1)
-            *reinterpret_cast<uint32_t*>(Bs + 0 * BN * kRowB + b_woff[h]) = a;
-            if constexpr (NPL >= 2) *reinterpret_cast<uint32_t*>(Bs + 1 * BN * kRowB + b_woff[h]) = b;
-            if constexpr (NPL == 3) *reinterpret_cast<uint32_t*>(Bs + 2 * BN * kRowB + b_woff[h]) = c;
+            for (int h = 0; h < BC / 2; h++) {
+                const float v0 = ((st.ok >> (2 * h)) & 1u) ? st.rb[2 * h] : 0.f, v1 = ((st.ok >> (2 * h + 1)) & 1u) ? st.rb[2 * h + 1] : 0.f;
+                // even lane gives away its second-column value and keeps the first; odd lane the other way round
+                const float give = odd ? v0 : v1, keep = odd ? v1 : v0;
+                const float got = __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(give), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+                uint32_t a, b, c;
+                split_words<NTERMS>(odd ? got : keep, odd ? keep : got, sb.s, a, b, c);        // (pixel k & ~1, pixel (k & ~1) + 1)
+                store_planes<NPL>(Bs + b_woff[h], BN * kRowB, a, b, c);
+            }
         }
     };
-    auto lread = [&](int buf) {
-        read_split_operands<WMB, WNB, BM, BN, NTERMS>(As0 + buf * T::a_bytes, Bs0 + buf * T::b_bytes, wm, wn, lane, O);
-    };
-
-    auto mma = [&]() {
-        if constexpr (F16) mma_split_h<WMB, WNB, NTERMS>(O, acc);
-        else               mma_split<WMB, WNB, NTERMS>(O, acc);
-    };
-
-    const int nkt = (kend - kbeg + BK - 1) / BK;
-    gload(kbeg, S[0]);
-    if (nkt > 1) gload(kbeg + BK, S[1]);
-    lstore(0, S[0]);
-    lds_barrier();
-    auto step_full = [&](int kt, Stage& s_same, Stage& s_next) {
-        lread(kt & 1);
-        gload(kbeg + (kt + 2) * BK, s_same);
-        lstore((kt + 1) & 1, s_next);
-        mma();
-        lds_barrier();
-    };
-    auto step_tail = [&](int kt, Stage& s_next, bool has_next) {
-        lread(kt & 1);
-        if (has_next) lstore((kt + 1) & 1, s_next);
-        mma();
-        if (has_next) lds_barrier();
-    };
-    int kt = 0;
-    for (; kt + 3 < nkt; kt += 2) {
-        step_full(kt, S[0], S[1]);
-        step_full(kt + 1, S[1], S[0]);
-    }
-    const int rem = nkt - kt;
-    if (rem == 3) {
-        step_full(kt, S[0], S[1]);
-        step_tail(kt + 1, S[0], true);
-        step_tail(kt + 2, S[1], false);
-    } else if (rem == 2) {
-        step_tail(kt, S[1], true);
-        step_tail(kt + 1, S[0], false);
-    } else {
-        step_tail(kt, S[1], false);
-    }
-
-    wgrad_store<WMB, WNB>(p, acc, F16 ? sa.inv * sb.inv : 1.f, grp, c_g, m0, n0, Nw, wm, wn, lane);
+    k_loop_split<T, WMB, WNB, NTERMS, Stage>((w.kend - w.kbeg + BK - 1) / BK, As0, Bs0, wm, wn, lane, acc, gload, lstore);
+    wgrad_store<WMB, WNB>(p, acc, F16 ? sa.inv * sb.inv : 1.f, w.grp, w.c_g, w.m0, w.n0, w.Nw, wm, wn, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1601,6 +1601,21 @@ static int split_terms()        // 0: fp32 MFMA engine; 6 / 3: bf16 products per
     return m == AG_CONV_MATH_SPLIT_BF16 ? 6 : m == AG_CONV_MATH_SPLIT_BF16X3 ? 3 : m == AG_CONV_MATH_SPLIT_F16 ? kF16 : m == AG_CONV_MATH_F16 ? kF16S : 0;
 }
 static bool split_math() { return split_terms() != 0; }
+
+// run-time choices -> the kernels' template arguments: f receives std::integral_constant's
+template <class F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_terms(int terms, F&& f)       // NTERMS of the split kernels (terms != 0)
+{
+    if (terms == 6)          f(std::integral_constant<int, 6>{});
+    else if (terms == 3)     f(std::integral_constant<int, 3>{});
+    else if (terms == kF16S) f(std::integral_constant<int, kF16S>{});
+    else                     f(std::integral_constant<int, kF16>{});
+}
+template <class F> static void with_tile(int bm, F&& f)           // (WMB, WNB): 64 x 256 or 128 x 128 outputs per workgroup of 2 x 4 waves
+{
+    if (bm == 64) f(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
+    else          f(std::integral_constant<int, 2>{}, std::integral_constant<int, 1>{});
+}
 
 // fp16 form: the partial maxima of a call's two operands live behind the split-K partial sums in the call's workspace
 constexpr size_t kAmaxBytes = 2 * (size_t)kMaxGroups * kAmaxParts * sizeof(float);
@@ -1654,6 +1669,16 @@ int conv_absmax(const AmaxTensor* t, int n, int G, float* out, hipStream_t s, fl
 }
 size_t conv_absmax_floats(int tensors) { return (size_t)tensors * kMaxGroups * kAmaxParts; }
 bool conv_math_needs_absmax() { return is_f16_form(split_terms()); }
+// fp16 forms: the partial maxima of a call's two operands -- the caller's where it already has them (pre_a / pre_b: ConvOpts), else swept
+// into `amax` (the call's workspace, behind the split-K partial sums)
+static int call_maxima(const AmaxTensor& ta, const AmaxTensor& tb, const float* pre_a, const float* pre_b, int G, float* amax, hipStream_t s,
+                          const float*& amax_a, const float*& amax_b)
+{
+    const AmaxTensor t[2] = { pre_a ? AmaxTensor{} : ta, pre_b ? AmaxTensor{} : tb };
+    amax_a = pre_a ? pre_a : amax;
+    amax_b = pre_b ? pre_b : amax + (size_t)kMaxGroups * kAmaxParts;
+    return conv_absmax(t, 2, G, amax, s);
+}
 
 // ag_conv_status: one pinned, mapped word per process (portable across devices); kernels store 1 into it, the host reads it without synchronising
 static int* status_word()
@@ -1797,15 +1822,11 @@ static int pack_and_launch(GatherProblem& gp, const TapSet* taps, int bm, const 
     gp.amax_a_mult = 1.f;
     if (f16 && skip_pack && !pre_w) { set_error("conv: frozen packed weights need their maxima (ConvOpts::amax_w)"); return AG_ERR_INVALID_ARGUMENT; }
     if (f16) {
-        AmaxTensor t[2] = { w_shape, AmaxTensor{ gp.xin, nullptr, gp.x_gs, (long long)gp.Cg * gp.Hg * gp.Wg, 0, 1 } };
-        t[0].table = &w;
-        if (pre_w) t[0] = AmaxTensor{};           // the caller already has this operand's partial maxima (ConvOpts)
-        if (pre_in) t[1] = AmaxTensor{};
-        int rc0 = conv_absmax(t, 2, G, amax, s);
+        AmaxTensor tw = w_shape;
+        tw.table = &w;
+        int rc0 = call_maxima(tw, AmaxTensor{ gp.xin, nullptr, gp.x_gs, (long long)gp.Cg * gp.Hg * gp.Wg, 0, 1 }, pre_w, pre_in, G, amax, s, gp.amax_a, gp.amax_b);
         if (rc0) return rc0;
-        pp.amax = pre_w ? pre_w : amax;
-        gp.amax_a = pp.amax;
-        gp.amax_b = pre_in ? pre_in : amax + (size_t)kMaxGroups * kAmaxParts;
+        pp.amax = gp.amax_a;
         gp.amax_a_mult = wscale != 1.f ? fabsf(wscale) : 1.f;
     }
     int rc = AG_OK;
@@ -1835,22 +1856,16 @@ static int pack_and_launch(GatherProblem& gp, const TapSet* taps, int bm, const 
     snprintf(tag, sizeof(tag), "g bm%d G%d M%d C%d N%d cls%d nkt%d sp%d wg%lld", bm, G, gp.M, gp.Cg, cols, gp.nclasses, nkt_max, splits,
              (long long)grid.x * grid.y * grid.z);
     ProfScope ps(AG_K_GATHER_CONV, s, flops, tag);      // covers the split-K finish too
-    if (split) {
-        const bool cexact = gp.Cg % BK == 0 && (size_t)gp.Cg * gp.Hg * gp.Wg * sizeof(float) < (size_t(1) << 32);
-#define AG_LAUNCH_SPLIT_T(WMB, WNB, CE, NTM) hipLaunchKernelGGL((gather_conv_split_kernel<WMB, WNB, 2, 4, CE, NTM>), grid, dim3(512), 0, s, gp)
-#define AG_LAUNCH_SPLIT(WMB, WNB, CE) do { if (terms == 6) AG_LAUNCH_SPLIT_T(WMB, WNB, CE, 6); else if (terms == 3) AG_LAUNCH_SPLIT_T(WMB, WNB, CE, 3); \
-                                           else if (terms == kF16S) AG_LAUNCH_SPLIT_T(WMB, WNB, CE, kF16S); else AG_LAUNCH_SPLIT_T(WMB, WNB, CE, kF16); } while (0)
-        if (bm == 64) {
-            if (cexact) AG_LAUNCH_SPLIT(1, 2, true); else AG_LAUNCH_SPLIT(1, 2, false);
-        } else {
-            if (cexact) AG_LAUNCH_SPLIT(2, 1, true); else AG_LAUNCH_SPLIT(2, 1, false);
-        }
-#undef AG_LAUNCH_SPLIT
-#undef AG_LAUNCH_SPLIT_T
-    } else {
-        if (bm == 64) hipLaunchKernelGGL((gather_conv_kernel<1, 2, 2, 4>), grid, dim3(512), 0, s, gp);
-        else          hipLaunchKernelGGL((gather_conv_kernel<2, 1, 2, 4>), grid, dim3(512), 0, s, gp);
-    }
+    const bool cexact = gp.Cg % BK == 0 && (size_t)gp.Cg * gp.Hg * gp.Wg * sizeof(float) < (size_t(1) << 32);
+    with_tile(bm, [&](auto wmb, auto wnb) {
+        constexpr int WMB = decltype(wmb)::value, WNB = decltype(wnb)::value;
+        if (!split) { hipLaunchKernelGGL((gather_conv_kernel<WMB, WNB, 2, 4>), grid, dim3(512), 0, s, gp); return; }
+        with_bool(cexact, [&](auto ce) {
+            with_terms(terms, [&](auto nt) {
+                hipLaunchKernelGGL((gather_conv_split_kernel<WMB, WNB, 2, 4, decltype(ce)::value, decltype(nt)::value>), grid, dim3(512), 0, s, gp);
+            });
+        });
+    });
     rc = check_hip(hipGetLastError(), "gather_conv_kernel");
     if (rc || splits == 1) return rc;
     const long long total = (long long)gp.M * cols;
@@ -2128,50 +2143,32 @@ int conv_backward_weight_g(const AgConvDesc* d, int G, const float* x, long long
     ProfScope ps(AG_K_WGRAD, s, 2.0 * G * wp.Mw * (double)Kp * Nw, tag);
     const bool avec = (Kp & 3) == 0;      // rows of A 16-byte aligned
     wp.amax_a = wp.amax_b = nullptr;
-    if (split_math()) {
-        const int terms = split_terms();
-        if (is_f16_form(terms)) {
-            if (!workspace || workspace_bytes < conv_workspace_bytes_g(d, G)) { set_error("conv workspace too small"); return AG_ERR_SCRATCH_TOO_SMALL; }
-            float* amax = reinterpret_cast<float*>(aligned_base(workspace) + (size_t)G * packed_bytes(d) + kMaxPartialBytes);
-            const bool conv = d->kind == AG_CONV;
-            const float* pre_a = conv ? o.amax_dy : o.amax_x;
-            const float* pre_b = conv ? o.amax_x : o.amax_dy;
-            AmaxTensor t[2] = { AmaxTensor{ wp.a, nullptr, wp.a_gs, (long long)wp.Mw * Kp, 0, 1 }, AmaxTensor{ wp.xin, nullptr, wp.xin_gs, (long long)wp.Cg * wp.Hg * wp.Wg, 0, 1 } };
-            if (pre_a) t[0] = AmaxTensor{};
-            if (pre_b) t[1] = AmaxTensor{};
-            if ((rc = conv_absmax(t, 2, G, amax, s))) return rc;
-            wp.amax_a = pre_a ? pre_a : amax;
-            wp.amax_b = pre_b ? pre_b : amax + (size_t)kMaxGroups * kAmaxParts;
-        }
-#define AG_LAUNCH_WSPLIT_T(WMB, WNB, AV, NTM) hipLaunchKernelGGL((wgrad_split_kernel<WMB, WNB, 2, 4, AV, NTM>), grid, dim3(512), 0, s, wp)
-#define AG_LAUNCH_WSPLIT_VT(WMB, WNB, NTM) hipLaunchKernelGGL((wgrad_split_kernel<WMB, WNB, 2, 4, true, NTM, true>), grid, dim3(512), 0, s, wp)
-#define AG_LAUNCH_WSPLIT(WMB, WNB, AV) do { if (terms == 6) AG_LAUNCH_WSPLIT_T(WMB, WNB, AV, 6); else if (terms == 3) AG_LAUNCH_WSPLIT_T(WMB, WNB, AV, 3); \
-                                            else if (terms == kF16S) AG_LAUNCH_WSPLIT_T(WMB, WNB, AV, kF16S); else AG_LAUNCH_WSPLIT_T(WMB, WNB, AV, kF16); } while (0)
-#define AG_LAUNCH_WSPLIT_V(WMB, WNB) do { if (terms == 6) AG_LAUNCH_WSPLIT_VT(WMB, WNB, 6); else if (terms == 3) AG_LAUNCH_WSPLIT_VT(WMB, WNB, 3); \
-                                          else if (terms == kF16S) AG_LAUNCH_WSPLIT_VT(WMB, WNB, kF16S); else AG_LAUNCH_WSPLIT_VT(WMB, WNB, kF16); } while (0)
-        // the K-vectorised loader of the gathered operand: stride-1 "same" convolutions with rows of a multiple of 16 pixels (every 3 x 3 stride-1
-        // layer of the product), whole K tiles per slice; every other shape takes the scalar gathers
-        const bool bvec = avec && d->kind == AG_CONV && d->stride == 1 && wp.gw == wp.Wg && wp.gh == wp.Hg && (wp.gw & 15) == 0 && wp.gw >= 16 &&
-                          (Kp & 15) == 0 && (wp.ksplit_len & 15) == 0 && 2 * d->padding + 1 == k && k <= 3;
-        if (bvec) {
-            if (bm == 64) AG_LAUNCH_WSPLIT_V(1, 2); else AG_LAUNCH_WSPLIT_V(2, 1);
-        } else
-        if (bm == 64) {
-            if (avec) AG_LAUNCH_WSPLIT(1, 2, true); else AG_LAUNCH_WSPLIT(1, 2, false);
-        } else {
-            if (avec) AG_LAUNCH_WSPLIT(2, 1, true); else AG_LAUNCH_WSPLIT(2, 1, false);
-        }
-#undef AG_LAUNCH_WSPLIT
-#undef AG_LAUNCH_WSPLIT_V
-#undef AG_LAUNCH_WSPLIT_T
-#undef AG_LAUNCH_WSPLIT_VT
-    } else if (bm == 64) {
-        if (avec) hipLaunchKernelGGL((wgrad_kernel<1, 2, 2, 4, true>), grid, dim3(512), 0, s, wp);
-        else      hipLaunchKernelGGL((wgrad_kernel<1, 2, 2, 4, false>), grid, dim3(512), 0, s, wp);
-    } else {
-        if (avec) hipLaunchKernelGGL((wgrad_kernel<2, 1, 2, 4, true>), grid, dim3(512), 0, s, wp);
-        else      hipLaunchKernelGGL((wgrad_kernel<2, 1, 2, 4, false>), grid, dim3(512), 0, s, wp);
+    const int terms = split_terms();
+    if (is_f16_form(terms)) {
+        if (!workspace || workspace_bytes < conv_workspace_bytes_g(d, G)) { set_error("conv workspace too small"); return AG_ERR_SCRATCH_TOO_SMALL; }
+        float* amax = reinterpret_cast<float*>(aligned_base(workspace) + (size_t)G * packed_bytes(d) + kMaxPartialBytes);
+        const bool conv = d->kind == AG_CONV;
+        if ((rc = call_maxima(AmaxTensor{ wp.a, nullptr, wp.a_gs, (long long)wp.Mw * Kp, 0, 1 },
+                                 AmaxTensor{ wp.xin, nullptr, wp.xin_gs, (long long)wp.Cg * wp.Hg * wp.Wg, 0, 1 }, conv ? o.amax_dy : o.amax_x,
+                                 conv ? o.amax_x : o.amax_dy, G, amax, s, wp.amax_a, wp.amax_b)))
+            return rc;
     }
+    // the K-vectorised loader of the gathered operand (split engine): stride-1 "same" convolutions with rows of a multiple of 16 pixels (every
+    // 3 x 3 stride-1 layer of the product), whole K tiles per slice; every other shape takes the scalar gathers
+    const bool bvec = avec && d->kind == AG_CONV && d->stride == 1 && wp.gw == wp.Wg && wp.gh == wp.Hg && (wp.gw & 15) == 0 && wp.gw >= 16 &&
+                      (Kp & 15) == 0 && (wp.ksplit_len & 15) == 0 && 2 * d->padding + 1 == k && k <= 3;
+    with_tile(bm, [&](auto wmb, auto wnb) {
+        constexpr int WMB = decltype(wmb)::value, WNB = decltype(wnb)::value;
+        if (terms == 0) {
+            with_bool(avec, [&](auto av) { hipLaunchKernelGGL((wgrad_kernel<WMB, WNB, 2, 4, decltype(av)::value>), grid, dim3(512), 0, s, wp); });
+            return;
+        }
+        with_terms(terms, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if (bvec) { hipLaunchKernelGGL((wgrad_split_kernel<WMB, WNB, 2, 4, true, NT, true>), grid, dim3(512), 0, s, wp); return; }
+            with_bool(avec, [&](auto av) { hipLaunchKernelGGL((wgrad_split_kernel<WMB, WNB, 2, 4, decltype(av)::value, NT>), grid, dim3(512), 0, s, wp); });
+        });
+    });
     if ((rc = check_hip(hipGetLastError(), "wgrad_kernel")) || !via_partial) return rc;
     wr.partial = wp.partial; wr.G = G; wr.splits = splits; wr.Mw = wp.Mw; wr.Nw = Nw; wr.Mpad = wp.Mpad; wr.Npad = wp.Npad; wr.ntaps = k2;
     wr.c_row_stride = wp.c_row_stride; wr.c_chan_stride = wp.c_chan_stride;

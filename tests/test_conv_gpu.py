@@ -64,8 +64,8 @@ def _close(a, b, name):
     assert (d <= lim).all(), f"{name}: max diff {d.max():.3e} (ref max {np.abs(b).max():.3e}), worst ratio {(d / lim).max():.2f}"
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
-def test_conv_forward_backward(case, math_mode):
+def _forward_backward(case, forward=lambda f: f(), backward=lambda f: f()):
+    """One case against torch's fp32 CPU convolution and autograd; ``forward`` / ``backward`` wrap the two device calls (_bracketed)."""
     import torch
     import torch.nn.functional as F
     from animatablegaussians_amd import conv as agc
@@ -80,13 +80,98 @@ def test_conv_forward_backward(case, math_mode):
     ref.backward(gy)
     xg, wg, bg = (t.detach().cuda().requires_grad_(True) for t in (x, w, b))
     fn = agc.conv2d if kind == "conv" else agc.conv_transpose2d
-    out = fn(xg, wg, bg, stride=stride, padding=padding)
+    out = forward(lambda: fn(xg, wg, bg, stride=stride, padding=padding))
     assert out.shape == ref.shape
     _close(out, ref, name + " forward")
-    out.backward(gy.cuda())
+    backward(lambda: out.backward(gy.cuda()))
     _close(xg.grad, x.grad, name + " dL/dx")
     _close(wg.grad, w.grad, name + " dL/dw")
     _close(bg.grad, b.grad, name + " dL/db")
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_conv_forward_backward(case, math_mode):
+    _forward_backward(case)
+
+
+# The K-loop drivers (k_loop_fp32 / k_loop_split in ag_conv.hip) prime two tiles, run pairs of tiles while at least four are left and finish
+# with one, two or three: 1 .. 5 K tiles per workgroup are the lone tail, two tails, three tails, loop + two, loop + three.  CASES reach none
+# of them (their shortest K loop has 9 tiles), so each path gets a case here, and each case reads the ag_prof record of its launch to make sure
+# that the kernel it is about ran, once, with the K-tile count it is about.
+def _bracketed(records_path):
+    """(wrapper, rows): wrapper(f) runs f() with the ag_prof brackets of the gather and weight-gradient kernels enabled and appends the
+    launches' records (dicts with kernel, tag, work, ms) to rows."""
+    import csv
+    import torch
+    from animatablegaussians_amd import _lib
+    rows = []
+
+    def wrapper(f):
+        torch.cuda.synchronize()
+        _lib.prof_enable([_lib.AG_K_GATHER_CONV, _lib.AG_K_WGRAD])
+        try:
+            _lib.prof_collect()                  # drop what an earlier test may have left
+            out = f()
+            torch.cuda.synchronize()
+            _lib.prof_collect_work(records_path)
+        finally:
+            _lib.prof_enable([])
+        rows.extend(csv.DictReader(open(records_path)))
+        return out
+    return wrapper, rows
+
+
+def _tag_fields(tag):
+    """'g bm64 G1 M64 C16 N72 cls1 nkt1 sp1 wg1' -> {'bm': 64, 'G': 1, 'M': 64, ...}"""
+    import re
+    return {m.group(1): int(m.group(2)) for m in (re.fullmatch(r"([A-Za-z]+?)(\d+)", t) for t in tag.split()[1:]) if m}
+
+
+@pytest.mark.parametrize("Cin", [16, 32, 48, 64, 80])
+def test_gather_k_loop_of_one_to_five_tiles(Cin, math_mode, tmp_path):
+    """1 x 1 convolutions over Cin = 16 nkt channels, 64 output rows (too many for the pointwise kernels), 8 x 9 pixels."""
+    wrapper, rows = _bracketed(tmp_path / "records.csv")
+    _forward_backward((f"nkt_gather_{Cin}", "conv", Cin, 64, 8, 9, 1, 1, 0), forward=wrapper)
+    tags = [r["tag"] for r in rows if r["tag"].startswith("g ")]
+    assert len(rows) == 1 and len(tags) == 1, rows
+    f = _tag_fields(tags[0])
+    assert (f["M"], f["C"], f["N"], f["cls"], f["nkt"], f["sp"]) == (64, Cin, 72, 1, Cin // 16, 1), tags
+
+
+WGRAD_NKT_CASES = [
+    # name, H, W, K tiles of the one slice.  Scalar loader of the gathered operand: rows that are no multiple of 16 pixels
+    ("scalar_4x4", 4, 4, 1), ("scalar_4x8", 4, 8, 2), ("scalar_6x8", 6, 8, 3), ("scalar_8x8", 8, 8, 4), ("scalar_8x10", 8, 10, 5),
+    # a ragged last tile, and rows of the other operand that are not 16-byte aligned (35 pixels: the scalar A loader as well)
+    ("scalar_5x7", 5, 7, 3),
+    # K-vectorised loader (the split engine's; stride-1 "same" convolution, 16-pixel rows): one K tile per image row
+    ("kvec_1x16", 1, 16, 1), ("kvec_2x16", 2, 16, 2), ("kvec_3x16", 3, 16, 3), ("kvec_4x16", 4, 16, 4), ("kvec_5x16", 5, 16, 5),
+]
+
+
+@pytest.mark.parametrize("case", WGRAD_NKT_CASES, ids=[c[0] for c in WGRAD_NKT_CASES])
+def test_wgrad_k_loop_of_one_to_five_tiles(case, math_mode, tmp_path):
+    """3 x 3 stride-1 padding-1 convolutions 16 -> 64 channels on images of 16 .. 80 pixels: one pixel slice of 1 .. 5 K tiles."""
+    name, H, W, nkt = case
+    wrapper, rows = _bracketed(tmp_path / "records.csv")
+    _forward_backward(("nkt_wgrad_" + name, "conv", 16, 64, H, W, 3, 1, 1), backward=wrapper)
+    tags = [r["tag"] for r in rows if r["tag"].startswith("w ")]
+    assert len(tags) == 1, rows
+    f = _tag_fields(tags[0])
+    # one slice of Kp pixels = ceil(Kp / 16) K tiles.  The record does not name the loader: the host gives the kvec_* shapes (16-pixel rows,
+    # whole tiles, one slice) to the K-vectorised kernel in the split modes and to the scalar one in the fp32 mode, which has no other.
+    assert (f["M"], f["C"], f["Kp"], f["t"], f["sp"]) == (64, 16, H * W, 9, 1) and (f["Kp"] + 15) // 16 == nkt, tags
+
+
+def test_gather_slice_without_k_tiles_writes_zeros(math_mode, tmp_path, monkeypatch):
+    """A stride-2 transposed convolution (parity classes of 4, 2, 2 and 1 taps, one K tile per tap at 16 channels) with its K loop cut in two:
+    the second slice has two tiles of the 4-tap class and none of the others, whose workgroups store zeros for the split-K sum."""
+    monkeypatch.setenv("AG_CONV_SPLITS", "2")        # the library reads it at every call
+    wrapper, rows = _bracketed(tmp_path / "records.csv")
+    _forward_backward(("nkt_gather_empty_slice", "convT", 16, 32, 9, 7, 3, 2, 0), forward=wrapper)
+    tags = [r["tag"] for r in rows if r["tag"].startswith("g ")]
+    assert len(rows) == 1 and len(tags) == 1, rows
+    f = _tag_fields(tags[0])
+    assert (f["M"], f["C"], f["cls"], f["nkt"]) == (32, 16, 4, 4) and f["sp"] == 2, tags
 
 
 @pytest.mark.parametrize("shape", [(64, 64, 20, 3, 1, 1), (3, 128, 16, 1, 1, 0), (128, 12, 16, 1, 1, 0), (32, 48, 19, 3, 2, 0)])
