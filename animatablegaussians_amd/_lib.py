@@ -195,6 +195,11 @@ class AgHandFieldFuseArgs(ctypes.Structure):  # include/ag_hand_fusion.h
                 + [("blob_floats", c_sz), ("left", AgHandSide), ("right", AgHandSide)])
 
 
+class AgRayCamera(ctypes.Structure):          # include/ag_ray_select.h
+    _fields_ = ([("inv_intr", c_f * 9), ("inv_rot", c_f * 9), ("cam", c_f * 3)] + [(n, c_f) for n in ("fx", "fy", "cx", "cy")]
+                + [("bounds", c_f * 6), ("W", c_i32), ("H", c_i32)])
+
+
 # every symbol include/*.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ag_abi_version", ctypes.c_int, []),
@@ -332,6 +337,13 @@ SYMBOLS = [
     ("ag_laplace_density_backward", ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_targets.h
     ("ag_prepare_targets", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # include/ag_ray_select.h
+    ("ag_ray_classify", ctypes.c_int, [ctypes.POINTER(c_i32), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    ("ag_ray_compact_workspace_bytes", c_sz, [ctypes.c_int64]),
+    ("ag_ray_compact", ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    ("ag_ray_camera_bytes", c_sz, []),
+    ("ag_ray_build", ctypes.c_int, [ctypes.POINTER(AgRayCamera), c_vp, c_vp, ctypes.c_int64] + [c_vp] * 13 + [c_vp]),
+    ("ag_ray_box_near_far", ctypes.c_int, [ctypes.POINTER(c_f), c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_styleunet.h
     ("ag_fused_bias_act", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_f, ctypes.c_int64, ctypes.c_int64, c_i32, c_vp]),
     ("ag_upfirdn2d", ctypes.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 13 + [c_vp]),

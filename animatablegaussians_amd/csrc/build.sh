@@ -70,6 +70,9 @@ compile "$HERE/ag_ray_march.hip" $EXACT &
 compile "$HERE/ag_ray_march_grad.hip" $EXACT &
 # the gates, the interpolation, the hand's signed distance, the blend and the density are stated op by op in include/ag_hand_fusion.h
 compile "$HERE/ag_hand_fusion.hip" $EXACT &
+# the ray, the six plane steps, near / far and dist are stated op by op in include/ag_ray_select.h and matched bit for bit by a numpy
+# float32 restatement: a fused multiply-add in `t * d + o` or in the sums of squares would round once where numpy rounds twice
+compile "$HERE/ag_ray_select.hip" $EXACT &
 fail=0
 for job in $(jobs -p); do wait "$job" || fail=1; done
 if [ "$fail" -ne 0 ]; then echo "build.sh: compilation failed" >&2; exit 1; fi

@@ -19,9 +19,9 @@ directions, the scattering through ``mask_within_patch``) around any differentia
 and mask L1 terms of ``main_template.py:37-51``.
 
 NOT here: the reverse pass of the fused MLP (``render_train`` takes a torch callable as the field until it exists), the eikonal
-term's second-order pass, the hand fusion's backward, gradients to ``z_vals``, and the dataset-side ray selection of ``nerf_util``
-(``get_rays``, ``get_near_far``, patch
-sampling): the caller brings the rays and the box near / far, as the reference's batch does.  Near / far is pinned to the header's
+term's second-order pass, the hand fusion's backward and gradients to ``z_vals``.  The rays and the box near / far are the caller's, as
+in the reference's batch; ``ray_select`` builds them on the device (``image_rays`` / ``render_image`` for a camera, ``sample_randomly`` /
+``sample_patches`` for a training batch from a frame).  Near / far of the SMPL-X balls is pinned to the header's
 formulas: the reference's kernel is CUDA and was never run beside this one.  Every tensor must be on the GPU; there is no host path
 and no PyTorch fallback.
 """
