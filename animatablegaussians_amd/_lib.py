@@ -321,6 +321,14 @@ SYMBOLS = [
     ("ag_template_field_forward", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     # include/ag_template_field_grad.h
     ("ag_template_field_sdf_grad", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
+    # include/ag_template_field_train.h
+    ("ag_template_field_train_slab", ctypes.c_int64, []),
+    ("ag_template_field_train_blob_t_floats", c_sz, [ctypes.POINTER(AgTemplateFieldDesc)]),
+    ("ag_template_field_train_stash_floats", c_sz, [ctypes.POINTER(AgTemplateFieldDesc), ctypes.c_int64]),
+    ("ag_template_field_train_workspace_floats", c_sz, [ctypes.POINTER(AgTemplateFieldDesc), ctypes.c_int64]),
+    ("ag_template_field_train_forward", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, c_vp, ctypes.c_int64, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    ("ag_template_field_train_backward", ctypes.c_int, [ctypes.POINTER(AgTemplateFieldDesc), c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, ctypes.c_int64, c_vp, c_sz,
+                                                        c_vp, c_vp, c_vp]),
     # include/ag_hand_fusion.h
     ("ag_hand_field_fuse_args_bytes", c_sz, []),
     ("ag_hand_fusion_blob_floats", c_sz, [ctypes.POINTER(AgHandFusionDesc)]),

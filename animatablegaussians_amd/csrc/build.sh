@@ -64,6 +64,8 @@ compile "$HERE/ag_isosurface.hip" $EXACT &
 # the embedding, the activations and the density are stated op by op in include/ag_template_field.h; the product sums are MFMA chains,
 # which contraction cannot touch
 compile "$HERE/ag_template_field.hip" $EXACT &
+# the training path repeats that embedding and those activations bit for bit (include/ag_template_field_train.h)
+compile "$HERE/ag_template_field_train.hip" $EXACT &
 # near / far, the sample positions and the compositing sums are stated op by op in include/ag_ray_march.h
 compile "$HERE/ag_ray_march.hip" $EXACT &
 # the reverse recurrence of the compositing and the density's derivatives are stated op by op in include/ag_ray_march_grad.h

@@ -10,7 +10,8 @@ reference template checkpoint becomes the mesh that ``obj_io.save_mesh_ply`` wri
 the reference's ``'normal'``, by a second fused kernel that pushes three tangents through the geometry MLP beside the value
 (``include/ag_template_field_grad.h``); ``eikonal_loss`` is ``main_template.py:53-58`` on it.
 
-NOT here: any gradient with respect to the weights (template training), any backward.  Ray sampling and compositing, the other half
+NOT here: the gradient with respect to the weights, which is ``template_train.TemplateFieldModule`` (a layer-wise path beside this fused
+kernel; ``module.to_field()`` comes back here); the eikonal term's second-order pass is not built.  Ray sampling and compositing, the other half
 of ``TemplateNet.render``, are ``template_render.py``; the hand fusion (``fuse_hands``, a checkpoint's ``left_hand.*`` / ``right_hand.*``) is
 ``hand_fusion.py``.  Every tensor must be on the GPU; there is no host path
 and no PyTorch fallback.

@@ -477,8 +477,8 @@ def render_train(field_fn, beta, ray_o: torch.Tensor, ray_d: torch.Tensor, near:
     """``TemplateNet.render`` in training mode for one batch element, differentiable with respect to whatever ``field_fn`` and ``beta``
     hold: ``render``'s rays, samplings, spaces and checks, then per chunk
 
-    ``field_fn(cano_pts [N, 3], viewdirs [N, 3]) -> (sdf [N, 1] or [N], color [N, 3])``, any differentiable callable (a torch module until
-    the fused field has a reverse pass), ``laplace_density(sdf, beta)`` and ``composite``.
+    ``field_fn(cano_pts [N, 3], viewdirs [N, 3]) -> (sdf [N, 1] or [N], color [N, 3])``, any differentiable callable
+    (``template_train.TemplateFieldModule``, whose forward and reverse pass are this project's kernels, or any torch module), ``laplace_density(sdf, beta)`` and ``composite``.
 
     ``u`` [R, S] perturbs the samples (``perturb = self.training``) and ``dir_noise`` [R * S, 3] (the reference's ``randn * 0.1``) is added
     to the unit view directions, which are normalised again (``template.py:358-362``); both are the caller's random numbers, and
